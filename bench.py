@@ -6,11 +6,17 @@ prep + K2 candidate evaluation (3 lanes x n_speeds, 50-point horizon, spline + l
 candidates IN TOTAL, sharded over the N GPUs (strong scaling: rank r evaluates the contiguous
 global scenes [r S/N, (r+1) S/N) of one seeded synthetic stream). No collective on the data path:
 the ranks meet only in the timing barrier and the max over ranks, both over gloo on the host.
-For N > 1 the line also carries a weak-scaling measurement (2,097,152 scenes per GPU).
 
-Run: python bench.py [--gpus N --steps K --warmup W]. Under torch.distributed.run (WORLD_SIZE set)
-each process is one rank; without it, --gpus N > 1 starts N rank processes itself (the parent
-never touches the GPU) and exits with their status.
+A plain run sets up, warms up, times the K steps and prints the result line (its roofline fields
+come from k_cand's events in the timed region and the committed profile summaries). --full adds
+the side measurements, each a run of its own after the headline: the pass with every kernel's
+events (k_prep, k_out), the host-buffer (PCIe-inclusive) pipeline, for N > 1 a weak-scaling
+measurement (2,097,152 scenes per GPU), config 5's shard projection and comfort mode, and the CPU
+baseline. --dump-outputs DIR writes the result arrays of the last timed step as DIR/<name>.npy.
+
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]. Under
+torch.distributed.run (WORLD_SIZE set) each process is one rank; without it, --gpus N > 1 starts N
+rank processes itself (the parent never touches the GPU) and exits with their status.
 """
 import argparse
 import json
@@ -247,6 +253,13 @@ def parse(argv=None):
                     help="skip timing config 5's 2-, 4- and 8-GPU shards after the headline (1 GPU, config 5)")
     ap.add_argument("--cpu-ranks", action="store_true",
                     help="launcher rehearsal without a GPU: every rank evaluates its shard with the CPU oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the side measurements: every kernel's events pass, the "
+                         "host-buffer (PCIe-inclusive) pipeline, weak scaling (N > 1), config 5's shard projection "
+                         "and comfort mode, and the CPU baseline (each still has its own --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result arrays of the last timed step to DIR/<name>.npy (float64; a fixed, "
+                         "seeded sample of the scenes where the whole batch exceeds the size budget)")
     return ap.parse_args(argv)
 
 
@@ -344,6 +357,37 @@ def chunk_bounds(S, chunks):
 
 
 OUT_FIELDS = ("winner", "n_out", "next_x", "next_y", "cost", "status")
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: all files of all ranks together (float64 elements)
+DUMP_SEED = 0xD0A1
+
+
+def dump_sample(S, bytes_per_scene, budget):
+    """Scene indices (sorted, int64) whose results --dump-outputs writes: every scene if the batch
+    fits the budget, else a fixed seeded sample (the same for every run with the same arguments)."""
+    k = max(1, min(S, budget // max(bytes_per_scene, 1)))
+    if k >= S:
+        return np.arange(S, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(S, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(res, out_dir, rank, world, first):
+    """Writes what the last pp_eval / pp_rollout left in the caller's result buffers as float64
+    <name>.npy files (rank r > 0: <name>.rank<r>.npy), plus scene_index.npy, the global scene index
+    of every row written. Integer outputs (winner, n_out, status words as unsigned, path_len) are
+    exact in float64. The scene axis is the last one of next_x/next_y and the first of the others."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    S = int(res["winner"].shape[0])
+    per_scene = sum(v.numel() // S for v in res.values()) * 8 + 8
+    idx = dump_sample(S, per_scene, DUMP_BUDGET_BYTES // world)
+    d_idx = torch.from_numpy(idx).to(res["winner"].device)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for name, v in res.items():
+        a = v.index_select(v.dim() - 1 if name in ("next_x", "next_y") else 0, d_idx).cpu().numpy()
+        if name == "status":
+            a = a.view(np.uint32)
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    np.save(os.path.join(out_dir, "scene_index" + suffix + ".npy"), (idx + first).astype(np.float64))
 
 
 def host_pipeline(m, scenes, prm, device, chunks, steps, warmup):
@@ -536,10 +580,12 @@ def main(argv=None):
     sp = stream.cuda_stream
     frames = max(a.rollout, 1)
 
-    def measure(first, S, steps, warmup, cost_mode=None):
+    def measure(first, S, steps, warmup, cost_mode=None, dump=None):
         """One timed run over this rank's shard: W untimed steps, then K steps bracketed by a
         barrier + device synchronisation on both sides; returns (max-over-ranks seconds, per-kernel
-        ms and launches of this rank, the resident scenes)."""
+        ms and launches of this rank, the resident scenes). `dump`: the directory that receives the
+        last timed step's results (--dump-outputs). The pass with every kernel's events runs only
+        under --full."""
         m.reserve(local, S * D)
         p = ppamd.default_params(n_speeds=a.n_speeds, n_points=a.n_points,
                                  cost_mode=prm.cost_mode if cost_mode is None else cost_mode,
@@ -578,11 +624,15 @@ def main(argv=None):
             dist.barrier()
         elapsed = time.perf_counter() - t0
         ms, launches = m.read_timing(local)
-        m.timing(local, ppamd.TIMING_ALL)
-        for _ in range(min(steps, 5)):
-            step()
-        torch.cuda.synchronize(dev)
-        ms_all, launches_all = m.read_timing(local)
+        if dump:
+            dump_outputs(res, dump, rank, world, first)
+        ms_all, launches_all = [0.0] * 3, [0] * 3
+        if a.full:
+            m.timing(local, ppamd.TIMING_ALL)
+            for _ in range(min(steps, 5)):
+                step()
+            torch.cuda.synchronize(dev)
+            ms_all, launches_all = m.read_timing(local)
         m.timing(local, False)
         del res
         return max_over_ranks(elapsed, dist), (ms, launches, ms_all, launches_all), scenes
@@ -593,10 +643,11 @@ def main(argv=None):
     else:
         first, S = shard(rank, world, per_rank=a.scenes)
         total_scenes = a.scenes * world
-    elapsed, (ms, launches, ms_all, launches_all), scenes = measure(first, S, a.steps, a.warmup)
+    elapsed, (ms, launches, ms_all, launches_all), scenes = measure(first, S, a.steps, a.warmup,
+                                                                    dump=a.dump_outputs)
     value = total_scenes * Cn * a.steps * frames / elapsed
     # per-rank kernel times (HIP events on each rank's launch streams): k_cand from the timed
-    # region, every kernel from the short pass after it
+    # region, every kernel from the short pass after it (--full; without it k_prep, k_out are None)
     kms = {"rank": rank, "scenes": S, "k_prep": (ms_all[0] / launches_all[0]) if launches_all[0] else None,
            "k_cand": ms[1] / max(launches[1], 1),
            "k_out": (ms_all[2] / launches_all[2]) if launches_all[2] else None,
@@ -606,7 +657,7 @@ def main(argv=None):
         per_rank = [None] * world
         dist.all_gather_object(per_rank, kms)
     pcie = None
-    if not (a.no_pcie or a.rollout or a.emit_paths or D > 1):
+    if a.full and not (a.no_pcie or a.rollout or a.emit_paths or D > 1):
         # side measurement, never `value`: the same batch handed over in pinned host buffers, every
         # rank its own shard through its own link; the job's step is the slowest rank's median step
         if dist:
@@ -632,7 +683,7 @@ def main(argv=None):
                     "what": "scenes in pinned host memory, H2D + pp_eval + D2H of winner, n_out, next_x/y, "
                             "costs, status; chunks pipelined over 3 streams; per-rank figures are rank 0's"}
     weak = None
-    if world > 1 and not a.no_weak and a.scaling == "strong":
+    if a.full and world > 1 and not a.no_weak and a.scaling == "strong":
         del scenes
         torch.cuda.empty_cache()
         wfirst, wS = shard(rank, world, per_rank=CONFIG5_SCENES)
@@ -656,6 +707,7 @@ def main(argv=None):
     pmc, rp, stamp = profile_entries(pmc, rp, ppamd.lib_sha256())
     traffic, traffic_pipe = roofline_fields(pmc, cands_launch, bpc, k_cand_ms)
     # the small-batch shapes run the whole step in one launch: its events time K1 + K2 + K4
+    # (known from the every-kernel pass, so under --full only)
     fused_step = bool(launches_all[1]) and not launches_all[0] and not a.rollout
     wname = workload_name(S, Cn, a.n_speeds, a.n_points, a.emit_paths, D, a.rollout)
     out = {
@@ -681,7 +733,7 @@ def main(argv=None):
         "kernels_ms_avg": {k: kms[k] for k in ("k_prep", "k_cand", "k_out")},
         "kernels_ms_source": ("k_cand: HIP events around each K2 launch in the timed region (the only events "
                               "there); k_prep, k_out: every kernel's events in a pass of min(steps, 5) steps "
-                              "after it"),
+                              "after it (--full only)"),
         "per_rank_kernels_ms": per_rank,
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
@@ -689,7 +741,9 @@ def main(argv=None):
                      "kernel_time_source": ("the whole one-launch step (K1 + K2 + K4 in one kernel: its "
                                             "dispatch's own start/end events), timed region" if fused_step else
                                             "HIP events around each K2 launch on its own stream, timed region "
-                                            "(a batch split over streams: the span of its parts' K2 launches)"),
+                                            "(a batch split over streams: the span of its parts' K2 launches)"
+                                            + ("" if a.full else "; a small batch that runs its whole step in one "
+                                               "launch times K1 + K2 + K4 (told apart under --full)")),
                      "profile_stamp": stamp,
                      "frac_rocprof": (bpc * cands_launch / (rp["dominant_ms_per_launch"] * 1e-3) / 1e9 / HBM_PEAK_GBS
                                       if rp else None),
@@ -728,7 +782,7 @@ def main(argv=None):
                                           "tools/valu_peak.hip"}
     if a.rollout:
         out["scene_frames_per_s"] = total_scenes * a.steps * frames / elapsed
-    if (world == 1 and a.scaling == "strong" and wname == "BASELINE config 5" and S == CONFIG5_SCENES
+    if (a.full and world == 1 and a.scaling == "strong" and wname == "BASELINE config 5" and S == CONFIG5_SCENES
             and not a.debug and not a.no_shard_projection):
         # the 2-, 4- and 8-GPU shards of the same batch, timed in this process on this GPU right
         # after the headline (same box, same build): the projected N-GPU speed-ups
@@ -741,7 +795,7 @@ def main(argv=None):
             "shards of 2,097,152 / N scenes (no collective); speed-up = min(t(full batch), N t(shard)) / "
             "t(shard), i.e. against the batch's best one-GPU policy (one call, or the N shards in "
             "sequence); all timed in this run (same protocol, steps and warmup)"))
-    if (world == 1 and a.scaling == "strong" and wname == "BASELINE config 5" and S == CONFIG5_SCENES
+    if (a.full and world == 1 and a.scaling == "strong" and wname == "BASELINE config 5" and S == CONFIG5_SCENES
             and not a.debug and not a.comfort and not a.no_comfort):
         # the data-dependent decision (north_star's "argmin per scene") on the same batch: the
         # comfort cost mode, where k_cand takes each scene's first-minimum cost and stores the
@@ -773,7 +827,7 @@ def main(argv=None):
                      "minimum of the 15 candidate costs (k_cand, in LDS), the winner's spline slot stored, "
                      "k_winner_st re-runs it with next_x/next_y; same timing protocol as the headline; "
                      "k_prep and k_winner from the pass after the timed region")}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.rollout:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not a.rollout:
         model, nproc, share = host_cpu()
         threads = a.cpu_threads or share
 

@@ -104,14 +104,14 @@ def test_launcher_starts_n_ranks():
 @pytest.mark.gpu
 def test_launcher_two_ranks_on_the_gpu():
     """`bench.py --gpus 2` on the GPU box: two rank processes (more ranks than GPUs share them), the
-    strong-scaling shards of one batch, gloo barrier + MAX, the PCIe leg on every rank, and the
-    weak-scaling side measurement; rank 0 reports n_gpus = 2 and both ranks' kernel times."""
+    strong-scaling shards of one batch, gloo barrier + MAX, and under --full the PCIe leg on every
+    rank and the weak-scaling side measurement; rank 0 reports n_gpus = 2 and both ranks' kernel times."""
     import json
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(oracle_lib.REPO, "bench.py"), "--gpus", "2", "--scenes", "65536",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--pcie-chunks", "2"],
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--pcie-chunks", "2"],
                        capture_output=True, text=True, env=env, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])

@@ -61,9 +61,9 @@ def test_host_build_equals_glibc():
     assert same(got, ref), (y[got != ref][:4], z[got != ref][:4])
 
 
-def test_standalone_checker():
+def test_standalone_checker(tmp_path):
     """tools/glibcm_check.cpp: 2 x 10^6 further arguments per function, compiled here."""
-    exe = "/tmp/pp_glibcm_check"
+    exe = str(tmp_path / "pp_glibcm_check")
     subprocess.run(["g++", "-O2", "-mfma", "-ffp-contract=off", "-fno-builtin-sin", "-fno-builtin-cos",
                     os.path.join(REPO, "tools", "glibcm_check.cpp"), "-o", exe, "-lm"], check=True)
     r = subprocess.run([exe, "1000000"], capture_output=True, text=True)

@@ -4,7 +4,7 @@
 # alternating runs; prints step and per-kernel ms (variants: libppamd_var_<name>.so)
 set -e -o pipefail
 R=$1; shift
-A=${ARGS:-}
+A="--full ${ARGS:-}"          # --full: the per-kernel pass behind the printed k_prep / k_out
 for i in $(seq $R); do
   for lib in default "$@"; do
     if [ $lib = default ]; then unset PPAMD_LIB; else export PPAMD_LIB=$PWD/carnd-path-planning-project_amd/ppamd/libppamd_var_$lib.so; fi

@@ -5,7 +5,7 @@ set -e
 T=${1:-r01}
 O=gpurun_out/$T
 mkdir -p $O
-run() { name=$1; shift; timeout -k 10 300 python3 bench.py "$@" > $O/$name.json 2> $O/$name.err; echo "$name: $(tail -1 $O/$name.json | cut -c1-160)"; }
+run() { name=$1; shift; timeout -k 10 300 python3 bench.py --full "$@" > $O/$name.json 2> $O/$name.err; echo "$name: $(tail -1 $O/$name.json | cut -c1-160)"; }
 run bench
 run bench_config2 --scenes 4096 --no-cpu-baseline
 run bench_config3_allpaths --emit-paths --n-speeds 8 --n-points 100 --scenes 262144 --no-cpu-baseline

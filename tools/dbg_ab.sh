@@ -5,7 +5,7 @@
 # per-kernel ms of each bench line.
 set -e -o pipefail
 R=$1; shift
-A=${ARGS:-}
+A="--full ${ARGS:-}"          # --full: the per-kernel pass behind the printed k_prep / k_out
 for i in $(seq $R); do
   for set in - "$@"; do
     D=""

@@ -27,7 +27,7 @@ python3 tools/rocprof_summarize.py $OUT/stats_1048576 k_cand_S1048576_C15_N50 3
 python3 tools/rocprof_summarize.py $OUT/stats4 k_cand_S16384_C192_N50_D64 1
 python3 tools/rocprof_summarize.py $OUT/stats2 k_cand_S4096_C15_N50 1
 cp profiles/rocprof_summary.json $OUT/rocprof_summary.json
-run() { name=$1; shift; timeout -k 10 300 python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name: $(tail -1 $OUT/$name.json | cut -c1-160)"; }
+run() { name=$1; shift; timeout -k 10 300 python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name: $(tail -1 $OUT/$name.json | cut -c1-160)"; }
 run bench
 run bench_config2 --scenes 4096 --steps 300 --warmup 30 --no-cpu-baseline
 run bench_config3_allpaths --emit-paths --n-speeds 8 --n-points 100 --scenes 262144 --no-cpu-baseline

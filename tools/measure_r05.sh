@@ -48,7 +48,7 @@ pm pmc4 k_cand_S16384_C192_N50_D64 --draws 64 --n-speeds 1 --scenes 16384
 bash tools/pmc.sh $OUT/pmc2 --steps 20 --warmup 5 $NP --scenes 4096 > $OUT/pmc2.log 2>&1
 python3 tools/pmc_summarize.py $OUT/pmc2 k_cand_S4096_C15_N50 > $OUT/pmc2_summary.txt
 cp profiles/pmc_summary.json $OUT/pmc_summary.json
-run() { name=$1; shift; timeout -k 10 400 python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name: $(tail -1 $OUT/$name.json | cut -c1-220)"; }
+run() { name=$1; shift; timeout -k 10 400 python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name: $(tail -1 $OUT/$name.json | cut -c1-220)"; }
 run bench
 run bench_config2 --scenes 4096 --steps 300 --warmup 30 --no-cpu-baseline
 run bench_config3_allpaths --emit-paths --n-speeds 8 --n-points 100 --scenes 262144 --no-cpu-baseline

@@ -56,7 +56,7 @@ cp profiles/pmc_summary.json $OUT/pmc_summary.json
 bash tools/pmc_stalls.sh $TAG
 python3 tools/pmc_stalls_summary.py $TAG profiles/r06_pmc_stalls.json > $OUT/stalls_summary.txt
 cp profiles/r06_pmc_stalls.json $OUT/
-run() { name=$1; shift; timeout -k 10 400 python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name: $(tail -1 $OUT/$name.json | cut -c1-220)"; }
+run() { name=$1; shift; timeout -k 10 400 python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name: $(tail -1 $OUT/$name.json | cut -c1-220)"; }
 run bench
 run bench_config2 --scenes 4096 --steps 300 --warmup 30 --no-cpu-baseline
 run bench_config3_allpaths --emit-paths --n-speeds 8 --n-points 100 --scenes 262144 --no-cpu-baseline

@@ -23,7 +23,7 @@ python3 tools/pmc_summarize.py $OUT/pmc4 k_cand_S16384_C192_N50_D64 > $OUT/pmc4_
 bash tools/pmc.sh $OUT/pmc2 --steps 20 --warmup 5 --no-cpu-baseline --no-pcie --scenes 4096
 python3 tools/pmc_summarize.py $OUT/pmc2 k_cand_S4096_C15_N50 > $OUT/pmc2_summary.txt
 cp profiles/pmc_summary.json $OUT/pmc_summary.json
-timeout -k 10 400 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 tail -1 $OUT/bench.json | cut -c1-300
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/stats -o run -- python3 $ROOT/bench.py --no-cpu-baseline --no-pcie > $OUT/bench_under_rocprof.json 2> $OUT/rocprof.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/stats3 -o run -- python3 $ROOT/bench.py --no-cpu-baseline --no-pcie --emit-paths --n-speeds 8 --n-points 100 --scenes 262144 > $OUT/bench3_under_rocprof.json 2> $OUT/rocprof3.err
@@ -38,7 +38,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/
  python3 tools/rocprof_summarize.py $OUT/stats2 k_cand_S4096_C15_N50 1)
 cp profiles/rocprof_summary.json $OUT/rocprof_summary.json
 echo "rocprof done"
-run() { name=$1; shift; timeout -k 10 300 python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name: $(tail -1 $OUT/$name.json | cut -c1-200)"; }
+run() { name=$1; shift; timeout -k 10 300 python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name: $(tail -1 $OUT/$name.json | cut -c1-200)"; }
 run bench_config2 --scenes 4096 --steps 300 --warmup 30 --no-cpu-baseline
 run bench_config3_allpaths --emit-paths --n-speeds 8 --n-points 100 --scenes 262144 --no-cpu-baseline
 run bench_config4_montecarlo --draws 64 --n-speeds 1 --scenes 16384 --no-cpu-baseline

@@ -6,6 +6,7 @@ shopt -s nullglob
 mkdir -p gpurun_out
 out=gpurun_out/variants.txt
 : > $out
+set -- --full "$@"     # --full: the per-kernel pass behind the printed kernels_ms_avg
 for lib in carnd-path-planning-project_amd/ppamd/libppamd.so carnd-path-planning-project_amd/ppamd/libppamd_var_*.so; do
   PPAMD_LIB=$PWD/$lib timeout -k 10 240 python bench.py --no-cpu-baseline "$@" > gpurun_out/vb.log 2>&1 || { echo "$lib FAILED" >> $out; tail -5 gpurun_out/vb.log >> $out; exit 1; }
   python - "$lib" >> $out <<'PY'
