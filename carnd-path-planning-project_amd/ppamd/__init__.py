@@ -348,7 +348,8 @@ def alloc_scenes(S, car_stride=12, xp="numpy", device=None):
 def scene_struct(d) -> SceneBatch:
     b = SceneBatch()
     b.n_scenes = int(d["ego_x"].shape[0])
-    b.car_stride = int(d["car_id"].shape[0])
+    # (car arrays of None: a batch without car columns, car_stride = 0 and null pointers)
+    b.car_stride = 0 if d["car_id"] is None else int(d["car_id"].shape[0])
     for k in SCENE_FIELDS_F + SCENE_FIELDS_I + CAR_FIELDS_F + ["prev_x", "prev_y", "car_id"]:
         setattr(b, k, _ptr(d[k]))
     for k in TABLE_FIELDS_I + TABLE_FIELDS_F:

@@ -323,7 +323,8 @@ def compare(got, ref, check_cost=True):
     and status words exact; every path point and next_x/next_y within TOL with an identical NaN
     pattern (the reference's standstill 0/0 NaN, src/main.cpp:1025, included: pp_glibcm.h makes
     the frame's trig the reference's libm bit for bit, so both sides take the same branch);
-    costs within 1e-9. Returns the largest |dxy|."""
+    next_x/next_y exactly 0 at every point i >= n_out[s] (include/pp.h; under PP_DBG_POISON an
+    unwritten point is a NaN); costs within 1e-9. Returns the largest |dxy|."""
     S, Cn = got["cost"].shape
     e = 0.0
     if "paths" in ref:
@@ -336,6 +337,9 @@ def compare(got, ref, check_cost=True):
     N = got["next_x"].shape[0]          # next_x/next_y are point-major [N][S]
     live = np.arange(N)[:, None] < got["n_out"][None, :]
     for k in ("next_x", "next_y"):
+        # points i >= n_out[s] are 0 (include/pp.h pp_result): written, not left as they were
+        pad = got[k][~live]
+        assert (pad == 0).all(), f"{k}: {int(np.count_nonzero(~(pad == 0)))} points beyond n_out are not 0"
         ee = max_err(np.where(live, got[k], 0.0), np.where(live, ref[k], 0.0))
         assert ee <= TOL, (k, ee)
         e = max(e, ee)
@@ -344,6 +348,45 @@ def compare(got, ref, check_cost=True):
     assert (got["status"] == ref["status"].view(np.uint32)).all(), \
         f"status differs in {int((got['status'] != ref['status'].view(np.uint32)).sum())} scenes"
     return e
+
+
+INFO_INT = ("ref_wp", "ego_lane", "target_lane", "lane_open_mask", "n_matched_cars", "in_lane_car")
+# double fields held bit for bit, and those with an absolute bound (lane_score: the project's 1e-12)
+INFO_BITS = ("ego_x", "ego_y", "ego_speed", "ego_acc", "ego_s", "ego_d", "ego_vs", "ego_vd", "ref_ratio")
+INFO_ABS = {"lane_score": 1e-12}
+
+
+def compare_info(got, ref):
+    """pp_scene_info of a pp_eval result against the oracle's (structured arrays, INFO_DTYPE):
+    every int field exact (_pad is not compared), identical NaN patterns, the double fields of
+    INFO_BITS bit for bit and those of INFO_ABS within their absolute bound. Returns {field:
+    largest |difference|} over the double fields; every figure is formed before anything is
+    asserted, and a failure's message carries all of them."""
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    bad = [k for k in INFO_INT if not np.array_equal(got[k], ref[k])]
+    errs, nan_bad, bit_bad = {}, [], []
+    for k in INFO_BITS + tuple(INFO_ABS):
+        a, b = np.ascontiguousarray(got[k]), np.ascontiguousarray(ref[k])
+        na, nb = np.isnan(a), np.isnan(b)
+        if not (na == nb).all():
+            nan_bad.append(k)
+        fin = ~(na | nb)
+        with np.errstate(invalid="ignore"):
+            d = np.abs(a[fin] - b[fin])
+        d = d[~np.isnan(d)]                    # (inf - inf: caught by the bit test / the bound below)
+        errs[k] = float(d.max()) if d.size else 0.0
+        same = (a.view(np.uint64) == b.view(np.uint64)) | (na & nb)
+        if k in INFO_BITS and not same.all():
+            bit_bad.append(f"{k} ({int((~same).sum())} values, max |d| {errs[k]:.3e})")
+        if k in INFO_ABS and not ((d <= INFO_ABS[k]).all() and (np.isinf(a) == np.isinf(b)).all()):
+            bit_bad.append(f"{k} (max |d| {errs[k]:.3e} > {INFO_ABS[k]:g})")
+    msg = {k: f"{v:.3e}" for k, v in errs.items()}
+    assert not bad, f"info int fields differ: " + ", ".join(
+        f"{k} in {int((got[k] != ref[k]).sum())} scenes (first {int(np.nonzero(got[k] != ref[k])[0][0])})"
+        for k in bad) + f"; double fields {msg}"
+    assert not nan_bad, f"info NaN pattern differs: {nan_bad}; {msg}"
+    assert not bit_bad, f"info double fields differ: {bit_bad}; all fields {msg}"
+    return errs
 
 
 def glibc_batch(olib, kind, a, b=None):

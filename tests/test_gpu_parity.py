@@ -325,9 +325,11 @@ def test_prep_group_invariance(env, case):
         for k, v in outs[1].items():
             assert same(outs[g][k], v), (g, k)
     if case != "draws":
-        ref = oracle_lib.oracle_eval(env["olib"], env["wx"], env["wy"], sc, prm, info=False)
+        ref = oracle_lib.oracle_eval(env["olib"], env["wx"], env["wy"], sc, prm, info=True)
         compare(outs[1], ref)
         compare(outs[16], ref)
+        oracle_lib.compare_info(outs[1]["info"], ref["info"])
+        oracle_lib.compare_info(outs[16]["info"], ref["info"])
 
 
 @pytest.mark.parametrize("case", ["random", "speed_edges"])
@@ -360,8 +362,9 @@ def test_fused_small_invariance(env, case):
     for name in ("k_cand_small", "step"):
         for k, v in outs["k_emit"].items():
             assert same(outs[name][k], v), (name, k)
-    ref = oracle_lib.oracle_eval(env["olib"], env["wx"], env["wy"], sc, prm, info=False)
+    ref = oracle_lib.oracle_eval(env["olib"], env["wx"], env["wy"], sc, prm, info=True)
     compare(outs["step"], ref)
+    oracle_lib.compare_info(outs["step"]["info"], ref["info"])
 
 
 @pytest.mark.parametrize("case", ["random", "ties_ids", "draws"])
