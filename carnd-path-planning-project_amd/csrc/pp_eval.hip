@@ -125,6 +125,7 @@ __device__ __forceinline__ unsigned long long trace_hwid() {
 #include "pp_glibcm.h"
 #include "pp_math.h"
 #include "pp_synth.h"
+#include "pp_judge.h"
 
 using namespace ppd;
 
@@ -3230,6 +3231,20 @@ __global__ __launch_bounds__(256) void k_sim(ppsynth::LaneTables LT, pp_scene_ba
     ((int32_t*)in.n_cars)[s] = nc;
 }
 
+// The rollout judge (include/pp.h pp_judge_frame; csrc/pp_judge.h): one lane per scene, every array
+// [k * S + s] so a wave's accesses are contiguous; no LDS, no scratch. Reads the pre-frame ego and
+// traffic and the frame's plan, so it runs between pp_eval and k_sim; writes only the judge state.
+__global__ __launch_bounds__(256) void k_judge(ppsynth::LaneTables LT, int64_t S, const double* ego_x,
+                                               const double* ego_y, const double* ego_yaw_deg,
+                                               const double* next_x, const double* next_y,
+                                               const int32_t* n_out, ppsynth::TrafficV tr, int consume,
+                                               pp_judge_cfg cfg, pp_judge st) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    ppjudge::judge_scene(LT, S, s, ego_x[s], ego_y[s], ego_yaw_deg[s], next_x, next_y, n_out[s], tr, consume,
+                         cfg, st);
+}
+
 __global__ __launch_bounds__(256) void k_synth_traffic(ppsynth::LaneTables T, uint64_t seed, int64_t first,
                                                        ppsynth::OutBatch o, ppsynth::TrafficV tr, pp_scene_batch tb) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3676,6 +3691,18 @@ ppsynth::OutBatch out_batch(const pp_scene_batch* b) {
 bool traffic_ok(const pp_traffic* t, const pp_scene_batch* b) {
     return t && b && t->n_cars >= 0 && t->n_cars <= PP_MAX_CARS && t->lane && t->seg && t->t &&
            t->offset && t->speed;
+}
+
+bool judge_ok(const pp_judge_cfg* c, const pp_judge* j) {
+    return c && j && ppjudge::cfg_ok(*c) && j->steps && j->flags && j->count && j->first_step &&
+           j->first_car && j->seg_hint && j->off_run && j->head_x && j->head_y && j->ring_vx && j->ring_vy &&
+           j->dist && j->clean_dist && j->min_sep && j->max_speed_mph && j->max_acc && j->max_jerk;
+}
+
+// what the judge reads of a frame: the ego pose, the traffic, the plan
+bool judge_frame_ok(const pp_scene_batch* tel, const pp_traffic* traffic, const pp_result* plan, int32_t consume) {
+    return tel && plan && tel->n_scenes >= 0 && tel->ego_x && tel->ego_y && tel->ego_yaw_deg &&
+           traffic_ok(traffic, tel) && plan->n_out && plan->next_x && plan->next_y && consume >= 1;
 }
 
 ppsynth::TrafficV traffic_view(const pp_traffic* t, int64_t S) {
@@ -4715,9 +4742,21 @@ int32_t pp_synth_traffic_host(const pp_map* M, uint64_t seed, int64_t first_scen
     return PP_OK;
 }
 
-int32_t pp_rollout(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
-                   const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
-                   void* hip_stream) {
+}  // extern "C"
+
+namespace {
+void launch_judge(const ppsynth::LaneTables& T, const pp_scene_batch* tel, const ppsynth::TrafficV& tv,
+                  const pp_result* plan, int32_t consume, const pp_judge_cfg* jc, const pp_judge* js,
+                  hipStream_t stream) {
+    const int64_t S = tel->n_scenes;
+    hipLaunchKernelGGL(k_judge, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, stream, T, S, tel->ego_x,
+                       tel->ego_y, tel->ego_yaw_deg, plan->next_x, plan->next_y, plan->n_out, tv, consume, *jc, *js);
+}
+
+// pp_rollout's loop; with a judge (jc, js non-null) k_judge runs between pp_eval and k_sim
+int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
+                     const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
+                     void* hip_stream, const pp_judge_cfg* jc, const pp_judge* js) {
     if (!M || !tel || !prm || !cfg || !res || device < 0 || device >= kMaxDev || !traffic_ok(traffic, tel))
         return PP_ERR_ARG;
     if (cfg->n_frames < 0 || cfg->consume < 1 || !(cfg->sensor_range >= 0) || prm->n_draws > 1 ||
@@ -4744,11 +4783,77 @@ int32_t pp_rollout(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp
     for (int f = 0; f < cfg->n_frames; f++) {
         const int rc = pp_eval(M, tel, prm, res, device, hip_stream);
         if (rc != PP_OK) return rc;
+        if (js) {
+            launch_judge(T, tel, tv, res, cfg->consume, jc, js, (hipStream_t)hip_stream);
+            if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
+        }
         A.frame = f;
         hipLaunchKernelGGL(k_sim, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, T, *tel,
                            tv, *prm, *res, A);
         if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
     }
+    return PP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t pp_rollout(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
+                   const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
+                   void* hip_stream) {
+    return rollout_loop(M, tel, traffic, prm, cfg, res, log, device, hip_stream, nullptr, nullptr);
+}
+
+int32_t pp_rollout_judged(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
+                          const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
+                          void* hip_stream, const pp_judge_cfg* jcfg, pp_judge* state) {
+    if (!judge_ok(jcfg, state) || !cfg || !judge_frame_ok(tel, traffic, res, cfg->consume)) return PP_ERR_ARG;
+    return rollout_loop(M, tel, traffic, prm, cfg, res, log, device, hip_stream, jcfg, state);
+}
+
+void pp_judge_cfg_default(pp_judge_cfg* c) {
+    if (!c) return;
+    memset(c, 0, sizeof(*c));
+    c->speed_limit_mph = 50;
+    c->max_acc = 10;
+    c->max_jerk = 10;
+    c->ego_length = c->car_length = 4.5;
+    c->ego_width = c->car_width = 2.0;
+    c->lane_tol = 1.0;
+    c->acc_window = 10;
+    c->jerk_window = 50;
+    c->off_lane_steps = 150;
+}
+
+int32_t pp_judge_frame(pp_map* M, const pp_scene_batch* tel, const pp_traffic* traffic, const pp_result* plan,
+                       int32_t consume, const pp_judge_cfg* cfg, pp_judge* state, int32_t device,
+                       void* hip_stream) {
+    if (!M || device < 0 || device >= kMaxDev || !judge_ok(cfg, state) ||
+        !judge_frame_ok(tel, traffic, plan, consume))
+        return PP_ERR_ARG;
+    if (tel->n_scenes == 0) return PP_OK;
+    DeviceGuard g(device);
+    ppsynth::LaneTables T;
+    {
+        std::lock_guard<std::mutex> lk(M->mu);
+        const int rc = dev_init(M, device);
+        if (rc) return rc;
+        T = lane_tables(M->dev[device].lanetab, M->n);
+    }
+    launch_judge(T, tel, traffic_view(traffic, tel->n_scenes), plan, consume, cfg, state, (hipStream_t)hip_stream);
+    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
+    return PP_OK;
+}
+
+int32_t pp_judge_frame_host(const pp_map* M, const pp_scene_batch* tel, const pp_traffic* traffic,
+                            const pp_result* plan, int32_t consume, const pp_judge_cfg* cfg, pp_judge* state) {
+    if (!M || !judge_ok(cfg, state) || !judge_frame_ok(tel, traffic, plan, consume)) return PP_ERR_ARG;
+    const ppsynth::LaneTables T = lane_tables(M->lanetab.data(), M->n);
+    const int64_t S = tel->n_scenes;
+    const ppsynth::TrafficV tv = traffic_view(traffic, S);
+    for (int64_t s = 0; s < S; s++)
+        ppjudge::judge_scene(T, S, s, tel->ego_x[s], tel->ego_y[s], tel->ego_yaw_deg[s], plan->next_x, plan->next_y,
+                             plan->n_out[s], tv, consume, *cfg, *state);
     return PP_OK;
 }
 

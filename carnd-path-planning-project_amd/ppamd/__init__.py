@@ -103,6 +103,29 @@ class RolloutLog(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _ in LOG_FIELDS] + [("plan_x", C.c_void_p), ("plan_y", C.c_void_p)]
 
 
+class JudgeCfg(C.Structure):
+    _fields_ = [("speed_limit_mph", C.c_double), ("max_acc", C.c_double), ("max_jerk", C.c_double),
+                ("ego_length", C.c_double), ("ego_width", C.c_double), ("car_length", C.c_double),
+                ("car_width", C.c_double), ("lane_tol", C.c_double), ("acc_window", C.c_int32),
+                ("jerk_window", C.c_int32), ("off_lane_steps", C.c_int32), ("_pad", C.c_int32)]
+
+
+# the rollout judge's state (include/pp.h pp_judge): name, dtype, leading dimension (None: [S])
+JUDGE_RING = 64
+INC_KINDS = ["COLLISION", "SPEED", "ACC", "JERK", "OFF_LANE"]      # kind k is flag bit 1 << k
+INC_COLLISION, INC_SPEED, INC_ACC, INC_JERK, INC_OFF_LANE = (1 << k for k in range(5))
+JUDGE_FIELDS = [("steps", "i4", None), ("flags", "u4", None), ("count", "i4", len(INC_KINDS)),
+                ("first_step", "i4", len(INC_KINDS)), ("first_car", "i4", None), ("seg_hint", "i4", None),
+                ("off_run", "i4", None), ("head_x", "f8", None), ("head_y", "f8", None),
+                ("ring_vx", "f8", JUDGE_RING), ("ring_vy", "f8", JUDGE_RING), ("dist", "f8", None),
+                ("clean_dist", "f8", None), ("min_sep", "f8", None), ("max_speed_mph", "f8", None),
+                ("max_acc", "f8", None), ("max_jerk", "f8", None)]
+
+
+class Judge(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _, _ in JUDGE_FIELDS]
+
+
 class Params(C.Structure):
     _fields_ = [("n_points", C.c_int32), ("n_speeds", C.c_int32), ("cost_mode", C.c_int32),
                 ("emit_paths", C.c_int32), ("speed_offsets", C.c_double * MAX_SPEEDS),
@@ -145,7 +168,8 @@ EXPORTS = ["pp_params_default", "pp_num_candidates", "pp_version", "pp_map_creat
            "pp_mc_gauss", "pp_rollout", "pp_synth_traffic", "pp_synth_traffic_host", "pp_plan_reset",
            "pp_telemetry_parse", "pp_control_format", "pp_plan_batch_host", "pp_serve", "pp_ws_accept_key",
            "pp_telemetry_parse_device", "pp_control_format_device", "pp_map_create_device",
-           "pp_num_lanes", "pp_max_cars", "pp_libm_eval", "pp_debug_set", "pp_debug_get"]
+           "pp_num_lanes", "pp_max_cars", "pp_libm_eval", "pp_debug_set", "pp_debug_get",
+           "pp_judge_cfg_default", "pp_judge_frame", "pp_judge_frame_host", "pp_rollout_judged"]
 
 
 def _load():
@@ -192,6 +216,18 @@ def _load():
                                C.POINTER(RolloutCfg), C.POINTER(Result), C.POINTER(RolloutLog), C.c_int32,
                                C.c_void_p]
     lib.pp_rollout.restype = C.c_int32
+    lib.pp_judge_cfg_default.argtypes = [C.POINTER(JudgeCfg)]
+    lib.pp_judge_cfg_default.restype = None
+    lib.pp_judge_frame.argtypes = [C.c_void_p, C.POINTER(SceneBatch), C.POINTER(Traffic), C.POINTER(Result),
+                                   C.c_int32, C.POINTER(JudgeCfg), C.POINTER(Judge), C.c_int32, C.c_void_p]
+    lib.pp_judge_frame.restype = C.c_int32
+    lib.pp_judge_frame_host.argtypes = [C.c_void_p, C.POINTER(SceneBatch), C.POINTER(Traffic), C.POINTER(Result),
+                                        C.c_int32, C.POINTER(JudgeCfg), C.POINTER(Judge)]
+    lib.pp_judge_frame_host.restype = C.c_int32
+    lib.pp_rollout_judged.argtypes = [C.c_void_p, C.POINTER(SceneBatch), C.POINTER(Traffic), C.POINTER(Params),
+                                      C.POINTER(RolloutCfg), C.POINTER(Result), C.POINTER(RolloutLog), C.c_int32,
+                                      C.c_void_p, C.POINTER(JudgeCfg), C.POINTER(Judge)]
+    lib.pp_rollout_judged.restype = C.c_int32
     lib.pp_synth_traffic.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.POINTER(SceneBatch),
                                      C.POINTER(Traffic), C.c_int32, C.c_void_p]
     lib.pp_synth_traffic.restype = C.c_int32
@@ -446,6 +482,69 @@ def rollout(m, scenes, traffic, prm, result, n_frames, consume=3, sensor_range=3
     L = log_struct(log) if log is not None else None
     _check(lib.pp_rollout(m.handle, C.byref(b), C.byref(T), C.byref(prm), C.byref(cfg), C.byref(R),
                           C.byref(L) if L is not None else None, device, stream), "pp_rollout")
+
+
+def default_judge_cfg(**over) -> JudgeCfg:
+    """pp_judge_cfg_default, with fields overridden by keyword."""
+    c = JudgeCfg()
+    lib.pp_judge_cfg_default(C.byref(c))
+    for k, v in over.items():
+        if k not in dict(JudgeCfg._fields_):
+            raise KeyError(k)
+        setattr(c, k, v)
+    return c
+
+
+def alloc_judge(S, xp="numpy", device=None):
+    """Zero-filled judge state of S scenes (every scene a fresh episode)."""
+    if xp == "numpy":
+        mk = lambda sh, dt: np.zeros(sh, dt)
+    else:
+        import torch
+        tdt = {"f8": torch.float64, "i4": torch.int32, "u4": torch.int32}
+        mk = lambda sh, dt: torch.zeros(sh, dtype=tdt[dt], device=device)
+    return {k: mk((S,) if lead is None else (lead, S), dt) for k, dt, lead in JUDGE_FIELDS}
+
+
+def judge_struct(j) -> Judge:
+    J = Judge()
+    for k, _, _ in JUDGE_FIELDS:
+        setattr(J, k, _ptr(j[k]))
+    return J
+
+
+def judge_to_numpy(j):
+    out = {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in j.items()}
+    out["flags"] = out["flags"].view(np.uint32)
+    return out
+
+
+def judge_frame(m, scenes, traffic, result, judge, consume=3, cfg=None, host=None, device=0, stream=None):
+    """pp_judge_frame / pp_judge_frame_host: judges the `consume` driven steps of one frame from the
+    pre-frame scenes and traffic and the frame's plan; only `judge` is updated. host=None picks the
+    host twin when the arrays are numpy."""
+    if host is None:
+        host = isinstance(scenes["ego_x"], np.ndarray)
+    cfg = cfg if cfg is not None else default_judge_cfg()
+    b, T, R, J = scene_struct(scenes), traffic_struct(traffic), result_struct(result), judge_struct(judge)
+    if host:
+        _check(lib.pp_judge_frame_host(m.handle, C.byref(b), C.byref(T), C.byref(R), consume, C.byref(cfg),
+                                       C.byref(J)), "pp_judge_frame_host")
+    else:
+        _check(lib.pp_judge_frame(m.handle, C.byref(b), C.byref(T), C.byref(R), consume, C.byref(cfg),
+                                  C.byref(J), device, stream), "pp_judge_frame")
+
+
+def rollout_judged(m, scenes, traffic, prm, result, judge, n_frames, consume=3, sensor_range=300.0, log=None,
+                   cfg=None, device=0, stream=None):
+    """pp_rollout_judged: rollout() with the judge run on every frame; `judge` updated in place."""
+    b, T, R, J = scene_struct(scenes), traffic_struct(traffic), result_struct(result), judge_struct(judge)
+    rc = RolloutCfg(n_frames, consume, float(sensor_range))
+    cfg = cfg if cfg is not None else default_judge_cfg()
+    L = log_struct(log) if log is not None else None
+    _check(lib.pp_rollout_judged(m.handle, C.byref(b), C.byref(T), C.byref(prm), C.byref(rc), C.byref(R),
+                                 C.byref(L) if L is not None else None, device, stream, C.byref(cfg),
+                                 C.byref(J)), "pp_rollout_judged")
 
 
 def plan_reset(m, device=0):

@@ -291,6 +291,86 @@ int32_t pp_rollout(pp_map* m, pp_scene_batch* telemetry, pp_traffic* traffic,
                    const pp_params* prm, const pp_rollout_cfg* cfg, pp_result* result,
                    pp_rollout_log* log, int32_t device, void* hip_stream);
 
+/* ---- rollout judge: incidents of a closed-loop drive ---------------------------------------- */
+/* The simulator this planner was written for counts the distance driven without an incident: a
+ * collision, more than 50 mph, total acceleration over 10 m/s^2, jerk over 10 m/s^3, or too long
+ * outside a lane. The simulator is not part of the reference, so the definitions here are THIS
+ * LIBRARY'S OWN, modelled on those published rules (DESIGN.md "Rollout judge" states them in
+ * full); nothing is or can be compared with the simulator. The judge looks at every driven step
+ * (0.02 s) of a frame: the ego's plan points against the limits, the lane-centre polylines and
+ * the rectangles of all traffic cars, whatever the sensor range. */
+#define PP_JUDGE_RING     64          /* velocity ring entries per scene (a power of two)          */
+#define PP_INC_KINDS      5           /* incident kinds: the bit numbers below                     */
+#define PP_INC_COLLISION  (1u << 0)   /* ego and car rectangles overlap (separating-axis sep <= 0) */
+#define PP_INC_SPEED      (1u << 1)   /* step speed > speed_limit_mph                              */
+#define PP_INC_ACC        (1u << 2)   /* |windowed acceleration| > max_acc                         */
+#define PP_INC_JERK       (1u << 3)   /* |windowed jerk| > max_jerk                                */
+#define PP_INC_OFF_LANE   (1u << 4)   /* more than off_lane_steps consecutive steps off every lane */
+
+typedef struct pp_judge_cfg {
+    double  speed_limit_mph;       /* 50                                                           */
+    double  max_acc;               /* 10 m/s^2                                                     */
+    double  max_jerk;              /* 10 m/s^3                                                     */
+    double  ego_length;            /* 4.5 m, along the heading                                     */
+    double  ego_width;             /* 2.0 m                                                        */
+    double  car_length;            /* 4.5 m, along the car's lane tangent                          */
+    double  car_width;             /* 2.0 m                                                        */
+    double  lane_tol;              /* 1.0 m: farther than this from every lane centre is off-lane  */
+    int32_t acc_window;            /* 10 steps: a_n = (v_n - v_{n-Wa}) / (Wa 0.02)                 */
+    int32_t jerk_window;           /* 50 steps: j_n = (a_n - a_{n-Wj}) / (Wj 0.02)                 */
+    int32_t off_lane_steps;        /* 150: the off-lane run may last this many steps               */
+    int32_t _pad;
+} pp_judge_cfg;                    /* 1 <= acc_window, 1 <= jerk_window, their sum <= 63           */
+
+/* Judge state of a batch (SoA, caller owned; device resident for pp_judge_frame and
+ * pp_rollout_judged, host memory for pp_judge_frame_host), S = the telemetry's n_scenes. Index
+ * conventions: per-scene scalars [s]; per-kind records [kind * S + s] (kind < PP_INC_KINDS, the bit
+ * number of PP_INC_*); ring entries [k * S + s] (k < PP_JUDGE_RING; the velocity of the episode's
+ * step n, 1-based, is entry n & (PP_JUDGE_RING - 1)). A scene whose steps[s] is 0 on entry starts
+ * a fresh episode: every other field of it is initialised by the call, so a zero-filled state is a
+ * valid start and a state is reused by zeroing `steps` alone. */
+typedef struct pp_judge {
+    int32_t*  steps;               /* driven steps judged so far (carried; 0 = fresh episode)      */
+    uint32_t* flags;               /* OR of PP_INC_* seen so far                                   */
+    int32_t*  count;               /* [kind * S + s] steps in violation                            */
+    int32_t*  first_step;          /* [kind * S + s] episode step of the first violation, 0: none  */
+    int32_t*  first_car;           /* traffic car of the first collision + 1, 0: none              */
+    int32_t*  seg_hint;            /* carried: lane-centre segment nearest to the ego              */
+    int32_t*  off_run;             /* carried: current run of consecutive off-lane steps           */
+    double*   head_x;              /* carried: unit heading of the last step that moved            */
+    double*   head_y;
+    double*   ring_vx;             /* carried: [k * S + s] step velocities (m/s)                   */
+    double*   ring_vy;
+    double*   dist;                /* metres driven                                                */
+    double*   clean_dist;          /* dist at the end of the last step before the first incident   */
+    double*   min_sep;             /* smallest separation to any car so far (+inf: none judged)    */
+    double*   max_speed_mph;       /* running maxima of the judged quantities                      */
+    double*   max_acc;
+    double*   max_jerk;
+} pp_judge;
+
+void    pp_judge_cfg_default(pp_judge_cfg* c);
+/* Judges the `consume` driven steps of ONE frame from the pre-frame state: `telemetry` (ego_x,
+ * ego_y, ego_yaw_deg are read) and `traffic` as they are before the simulator moves them, `plan`
+ * (n_out, next_x, next_y) as pp_eval wrote it. For callers that run their own loop around pp_eval:
+ * call it after pp_eval and before moving the ego and the traffic. Nothing but `state` is written.
+ * The traffic is trusted as pp_rollout trusts it: every car's lane < PP_NUM_LANES and 0 <= seg <
+ * the map's waypoint count are the caller's duty (they index the lane tables unchecked), and
+ * n_out[s] must not exceed the points next_x/next_y hold. Device pointers; asynchronous on
+ * hip_stream. */
+int32_t pp_judge_frame(pp_map* m, const pp_scene_batch* telemetry, const pp_traffic* traffic,
+                       const pp_result* plan, int32_t consume, const pp_judge_cfg* cfg, pp_judge* state,
+                       int32_t device, void* hip_stream);
+/* The same on the host (host pointers; the same arithmetic, bit for bit). */
+int32_t pp_judge_frame_host(const pp_map* m, const pp_scene_batch* telemetry, const pp_traffic* traffic,
+                            const pp_result* plan, int32_t consume, const pp_judge_cfg* cfg, pp_judge* state);
+/* pp_rollout with the judge: per frame pp_eval, the judge, then the simulator, on the one stream.
+ * Everything pp_rollout writes is written exactly as pp_rollout writes it. */
+int32_t pp_rollout_judged(pp_map* m, pp_scene_batch* telemetry, pp_traffic* traffic,
+                          const pp_params* prm, const pp_rollout_cfg* cfg, pp_result* result,
+                          pp_rollout_log* log, int32_t device, void* hip_stream,
+                          const pp_judge_cfg* jcfg, pp_judge* state);
+
 /* Rollout start state: writes the synthetic scenes of pp_synth_scenes (same seed and indices)
  * into `telemetry` and their traffic into `out` (n_cars = 12): car j starts exactly where the
  * scene reports it, on its lane with its lateral offset and speed. Empties the car table of
