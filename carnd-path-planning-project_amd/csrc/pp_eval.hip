@@ -126,6 +126,7 @@ __device__ __forceinline__ unsigned long long trace_hwid() {
 #include "pp_math.h"
 #include "pp_synth.h"
 #include "pp_judge.h"
+#include "pp_follow.h"
 
 using namespace ppd;
 
@@ -3245,6 +3246,18 @@ __global__ __launch_bounds__(256) void k_judge(ppsynth::LaneTables LT, int64_t S
                          cfg, st);
 }
 
+// Reactive traffic (include/pp.h pp_traffic_follow; csrc/pp_follow.h): one lane per scene, every array
+// [k * S + s]; no LDS, no scratch. Reads the pre-frame ego and traffic, so it runs before k_judge and
+// k_sim; writes the traffic's speeds and the follow state.
+__global__ __launch_bounds__(256) void k_follow(ppsynth::LaneTables LT, ppfollow::ArcTables AT, int64_t S,
+                                                const double* ego_x, const double* ego_y,
+                                                const double* ego_speed_mph, ppsynth::TrafficV tr, int consume,
+                                                pp_follow_cfg cfg, pp_follow st) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    ppfollow::follow_scene(LT, AT, S, s, ego_x[s], ego_y[s], ego_speed_mph[s], tr, consume, cfg, st);
+}
+
 __global__ __launch_bounds__(256) void k_synth_traffic(ppsynth::LaneTables T, uint64_t seed, int64_t first,
                                                        ppsynth::OutBatch o, ppsynth::TrafficV tr, pp_scene_batch tb) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3378,6 +3391,7 @@ struct DevState {
     double2* wseg = nullptr;      // reference segment lengths and reciprocals (pp_map::wseg)
     double* atab = nullptr;       // the approach table (pp_map::atab)
     double* lanetab = nullptr;    // synth tables: lc_x[NL n] lc_y[NL n] seg_len[NL n] tan_x[NL n] tan_y[NL n]
+    double* arctab = nullptr;     // pp_map::arctab, uploaded on the first follow call (arc_init)
     std::map<void*, StreamWS> sws;  // per hip_stream
     void* frame = nullptr;        // single-frame scratch (pp_plan_frame)
     void* frame_host = nullptr;   // its pinned host staging copy (coherent: k_plan_frame reads and
@@ -3407,6 +3421,7 @@ struct pp_map {
     std::vector<double> geom;     // kMapArrays * n (MapG layout)
     std::vector<double> ptab;     // (4 + 2 NL) * n: ref xy, normal, lane centres (pp_map_geometry)
     std::vector<double> lanetab;  // 5 NL * n
+    std::vector<double> arctab;   // reactive traffic's arc prefix (ppfollow::build_arc): cum[NL n] loop[NL]
     int fastm = 0;                // MapV::fastm: bit 1: every lane segment's rdenom in [2^-500, 2^500]; bit 2: approach_seg's map bounds
     std::vector<uint2> wgrid;     // closest-waypoint cell table (build_wgrid; empty: none)
     std::vector<double2> wseg;    // reference segment lengths and reciprocals (build_wseg; empty: none)
@@ -3423,6 +3438,13 @@ struct DeviceGuard {
     explicit DeviceGuard(int d) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(d); }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+
+// reactive traffic's arc prefix from the host lanetab's seg_len (for a pp_map_create_device map: the
+// mirrored device values), one left-to-right sum per lane
+void fill_arctab(pp_map* M) {
+    M->arctab.assign(ppfollow::arc_doubles(M->n), 0.0);
+    ppfollow::build_arc(M->lanetab.data() + 2 * NL * (size_t)M->n, M->n, M->arctab.data());
+}
 
 // pp_map_geometry's table from the MapG layout: per waypoint ref xy, normal, lane centres
 void fill_ptab(pp_map* M) {
@@ -3672,6 +3694,7 @@ int build_map(pp_map* M, const double* wx, const double* wy, int n) {
             t[3 * NL * n + r * n + i] = (lcx[r * n + i] - lcx[r * n + p]) / len;
             t[4 * NL * n + r * n + i] = (lcy[r * n + i] - lcy[r * n + p]) / len;
         }
+    fill_arctab(M);
     return PP_OK;
 }
 
@@ -3705,6 +3728,17 @@ bool judge_frame_ok(const pp_scene_batch* tel, const pp_traffic* traffic, const 
            traffic_ok(traffic, tel) && plan->n_out && plan->next_x && plan->next_y && consume >= 1;
 }
 
+bool follow_ok(const pp_follow_cfg* c, const pp_follow* f) {
+    return c && f && ppfollow::cfg_ok(*c) && f->started && f->ego_seg && f->desired && f->next_speed &&
+           f->leader && f->gap;
+}
+
+// what the follow update reads of a frame: the ego's position and speed, the traffic
+bool follow_frame_ok(const pp_scene_batch* tel, const pp_traffic* traffic, int32_t consume) {
+    return tel && tel->n_scenes >= 0 && tel->ego_x && tel->ego_y && tel->ego_speed_mph &&
+           traffic_ok(traffic, tel) && consume >= 1;
+}
+
 ppsynth::TrafficV traffic_view(const pp_traffic* t, int64_t S) {
     ppsynth::TrafficV v;
     v.S = S; v.n = t->n_cars; v.lane = t->lane; v.seg = t->seg; v.t = t->t; v.off = t->offset; v.v = t->speed;
@@ -3728,6 +3762,20 @@ int dev_init(pp_map* M, int device) {
     const int rc = upload_wgrid(M, D);
     if (rc != PP_OK) return rc;
     D.init = true;
+    return PP_OK;
+}
+
+// the device copy of the arc prefix, made on the first follow call on this device (after dev_init,
+// under M->mu)
+int arc_init(pp_map* M, int device) {
+    DevState& D = M->dev[device];
+    if (D.arctab) return PP_OK;
+    if (hipMalloc(&D.arctab, sizeof(double) * M->arctab.size()) != hipSuccess) return PP_ERR_NOMEM;
+    if (hipMemcpy(D.arctab, M->arctab.data(), sizeof(double) * M->arctab.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(D.arctab);
+        D.arctab = nullptr;
+        return PP_ERR_HIP;
+    }
     return PP_OK;
 }
 
@@ -4151,6 +4199,7 @@ static int32_t map_create_device(const double* d_wx, const double* d_wy, int32_t
     }
     fill_ptab(M);
     build_tables(M);
+    fill_arctab(M);
     if (upload_wgrid(M, D) != PP_OK) {
         free_map_tables(D);
         (void)hipFree(D.map); (void)hipFree(D.lanetab);
@@ -4170,6 +4219,7 @@ int32_t pp_map_destroy(pp_map* M) {
         DeviceGuard g(d);
         (void)hipDeviceSynchronize();
         (void)hipFree(D.map); (void)hipFree(D.lanetab);
+        if (D.arctab) (void)hipFree(D.arctab);
         free_map_tables(D);
         for (auto& kv : D.sws) free_ws(kv.second);
         D.sws.clear();
@@ -4753,10 +4803,20 @@ void launch_judge(const ppsynth::LaneTables& T, const pp_scene_batch* tel, const
                        tel->ego_y, tel->ego_yaw_deg, plan->next_x, plan->next_y, plan->n_out, tv, consume, *jc, *js);
 }
 
-// pp_rollout's loop; with a judge (jc, js non-null) k_judge runs between pp_eval and k_sim
+void launch_follow(const ppsynth::LaneTables& T, const ppfollow::ArcTables& AT, const pp_scene_batch* tel,
+                   const ppsynth::TrafficV& tv, int32_t consume, const pp_follow_cfg* fc, const pp_follow* fs,
+                   hipStream_t stream) {
+    const int64_t S = tel->n_scenes;
+    hipLaunchKernelGGL(k_follow, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, stream, T, AT, S, tel->ego_x,
+                       tel->ego_y, tel->ego_speed_mph, tv, consume, *fc, *fs);
+}
+
+// pp_rollout's loop; with follow state (fc, fs non-null) k_follow runs after pp_eval, with a judge (jc,
+// js non-null) k_judge runs before k_sim
 int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
                      const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
-                     void* hip_stream, const pp_judge_cfg* jc, const pp_judge* js) {
+                     void* hip_stream, const pp_judge_cfg* jc, const pp_judge* js,
+                     const pp_follow_cfg* fc = nullptr, const pp_follow* fs = nullptr) {
     if (!M || !tel || !prm || !cfg || !res || device < 0 || device >= kMaxDev || !traffic_ok(traffic, tel))
         return PP_ERR_ARG;
     if (cfg->n_frames < 0 || cfg->consume < 1 || !(cfg->sensor_range >= 0) || prm->n_draws > 1 ||
@@ -4768,11 +4828,17 @@ int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const 
     if (tel->n_scenes == 0 || cfg->n_frames == 0) return PP_OK;
     DeviceGuard g(device);
     ppsynth::LaneTables T;
+    ppfollow::ArcTables AT = {nullptr, nullptr};
     {
         std::lock_guard<std::mutex> lk(M->mu);
         const int rc = dev_init(M, device);
         if (rc) return rc;
         T = lane_tables(M->dev[device].lanetab, M->n);
+        if (fs) {
+            const int ra = arc_init(M, device);
+            if (ra) return ra;
+            AT = ppfollow::arc_tables(M->dev[device].arctab, M->n);
+        }
     }
     SimArgs A;
     A.consume = cfg->consume;
@@ -4783,6 +4849,10 @@ int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const 
     for (int f = 0; f < cfg->n_frames; f++) {
         const int rc = pp_eval(M, tel, prm, res, device, hip_stream);
         if (rc != PP_OK) return rc;
+        if (fs) {
+            launch_follow(T, AT, tel, tv, cfg->consume, fc, fs, (hipStream_t)hip_stream);
+            if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
+        }
         if (js) {
             launch_judge(T, tel, tv, res, cfg->consume, jc, js, (hipStream_t)hip_stream);
             if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
@@ -4854,6 +4924,66 @@ int32_t pp_judge_frame_host(const pp_map* M, const pp_scene_batch* tel, const pp
     for (int64_t s = 0; s < S; s++)
         ppjudge::judge_scene(T, S, s, tel->ego_x[s], tel->ego_y[s], tel->ego_yaw_deg[s], plan->next_x, plan->next_y,
                              plan->n_out[s], tv, consume, *cfg, *state);
+    return PP_OK;
+}
+
+int32_t pp_rollout_reactive(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
+                            const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
+                            void* hip_stream, const pp_judge_cfg* jcfg, pp_judge* jstate,
+                            const pp_follow_cfg* fcfg, pp_follow* fstate) {
+    if (!follow_ok(fcfg, fstate) || !cfg || !follow_frame_ok(tel, traffic, cfg->consume)) return PP_ERR_ARG;
+    if (jstate && (!judge_ok(jcfg, jstate) || !judge_frame_ok(tel, traffic, res, cfg->consume))) return PP_ERR_ARG;
+    return rollout_loop(M, tel, traffic, prm, cfg, res, log, device, hip_stream, jstate ? jcfg : nullptr, jstate,
+                        fcfg, fstate);
+}
+
+void pp_follow_cfg_default(pp_follow_cfg* c) {
+    if (!c) return;
+    memset(c, 0, sizeof(*c));
+    c->max_acc = 2.0;
+    c->comfort_brake = 3.0;
+    c->max_brake = 8.0;
+    c->time_headway = 1.2;
+    c->min_gap = 2.0;
+    c->gap_floor = 0.5;
+    c->horizon = 150;
+    c->car_length = c->ego_length = 4.5;
+    c->lateral_reach = 2.0;
+    c->react_to_ego = 1;
+}
+
+int32_t pp_traffic_follow(pp_map* M, const pp_scene_batch* tel, pp_traffic* traffic, int32_t consume,
+                          const pp_follow_cfg* cfg, pp_follow* state, int32_t device, void* hip_stream) {
+    if (!M || device < 0 || device >= kMaxDev || !follow_ok(cfg, state) || !follow_frame_ok(tel, traffic, consume))
+        return PP_ERR_ARG;
+    if (tel->n_scenes == 0) return PP_OK;
+    DeviceGuard g(device);
+    ppsynth::LaneTables T;
+    ppfollow::ArcTables AT;
+    {
+        std::lock_guard<std::mutex> lk(M->mu);
+        int rc = dev_init(M, device);
+        if (rc) return rc;
+        rc = arc_init(M, device);
+        if (rc) return rc;
+        T = lane_tables(M->dev[device].lanetab, M->n);
+        AT = ppfollow::arc_tables(M->dev[device].arctab, M->n);
+    }
+    launch_follow(T, AT, tel, traffic_view(traffic, tel->n_scenes), consume, cfg, state, (hipStream_t)hip_stream);
+    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
+    return PP_OK;
+}
+
+int32_t pp_traffic_follow_host(const pp_map* M, const pp_scene_batch* tel, pp_traffic* traffic, int32_t consume,
+                               const pp_follow_cfg* cfg, pp_follow* state) {
+    if (!M || !follow_ok(cfg, state) || !follow_frame_ok(tel, traffic, consume)) return PP_ERR_ARG;
+    const ppsynth::LaneTables T = lane_tables(M->lanetab.data(), M->n);
+    const ppfollow::ArcTables AT = ppfollow::arc_tables(M->arctab.data(), M->n);
+    const int64_t S = tel->n_scenes;
+    const ppsynth::TrafficV tv = traffic_view(traffic, S);
+    for (int64_t s = 0; s < S; s++)
+        ppfollow::follow_scene(T, AT, S, s, tel->ego_x[s], tel->ego_y[s], tel->ego_speed_mph[s], tv, consume, *cfg,
+                               *state);
     return PP_OK;
 }
 

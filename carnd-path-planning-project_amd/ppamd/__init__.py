@@ -126,6 +126,22 @@ class Judge(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in JUDGE_FIELDS]
 
 
+class FollowCfg(C.Structure):
+    _fields_ = [("max_acc", C.c_double), ("comfort_brake", C.c_double), ("max_brake", C.c_double),
+                ("time_headway", C.c_double), ("min_gap", C.c_double), ("gap_floor", C.c_double),
+                ("horizon", C.c_double), ("car_length", C.c_double), ("ego_length", C.c_double),
+                ("lateral_reach", C.c_double), ("react_to_ego", C.c_int32), ("_pad", C.c_int32)]
+
+
+# reactive traffic's state (include/pp.h pp_follow): name, dtype, per car ([n, S]) or per scene ([S])
+FOLLOW_FIELDS = [("started", "i4", False), ("ego_seg", "i4", False), ("desired", "f8", True),
+                 ("next_speed", "f8", True), ("leader", "i4", True), ("gap", "f8", True)]
+
+
+class Follow(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _, _ in FOLLOW_FIELDS]
+
+
 class Params(C.Structure):
     _fields_ = [("n_points", C.c_int32), ("n_speeds", C.c_int32), ("cost_mode", C.c_int32),
                 ("emit_paths", C.c_int32), ("speed_offsets", C.c_double * MAX_SPEEDS),
@@ -169,7 +185,8 @@ EXPORTS = ["pp_params_default", "pp_num_candidates", "pp_version", "pp_map_creat
            "pp_telemetry_parse", "pp_control_format", "pp_plan_batch_host", "pp_serve", "pp_ws_accept_key",
            "pp_telemetry_parse_device", "pp_control_format_device", "pp_map_create_device",
            "pp_num_lanes", "pp_max_cars", "pp_libm_eval", "pp_debug_set", "pp_debug_get",
-           "pp_judge_cfg_default", "pp_judge_frame", "pp_judge_frame_host", "pp_rollout_judged"]
+           "pp_judge_cfg_default", "pp_judge_frame", "pp_judge_frame_host", "pp_rollout_judged",
+           "pp_follow_cfg_default", "pp_traffic_follow", "pp_traffic_follow_host", "pp_rollout_reactive"]
 
 
 def _load():
@@ -228,6 +245,19 @@ def _load():
                                       C.POINTER(RolloutCfg), C.POINTER(Result), C.POINTER(RolloutLog), C.c_int32,
                                       C.c_void_p, C.POINTER(JudgeCfg), C.POINTER(Judge)]
     lib.pp_rollout_judged.restype = C.c_int32
+    lib.pp_follow_cfg_default.argtypes = [C.POINTER(FollowCfg)]
+    lib.pp_follow_cfg_default.restype = None
+    lib.pp_traffic_follow.argtypes = [C.c_void_p, C.POINTER(SceneBatch), C.POINTER(Traffic), C.c_int32,
+                                      C.POINTER(FollowCfg), C.POINTER(Follow), C.c_int32, C.c_void_p]
+    lib.pp_traffic_follow.restype = C.c_int32
+    lib.pp_traffic_follow_host.argtypes = [C.c_void_p, C.POINTER(SceneBatch), C.POINTER(Traffic), C.c_int32,
+                                           C.POINTER(FollowCfg), C.POINTER(Follow)]
+    lib.pp_traffic_follow_host.restype = C.c_int32
+    lib.pp_rollout_reactive.argtypes = [C.c_void_p, C.POINTER(SceneBatch), C.POINTER(Traffic), C.POINTER(Params),
+                                        C.POINTER(RolloutCfg), C.POINTER(Result), C.POINTER(RolloutLog), C.c_int32,
+                                        C.c_void_p, C.POINTER(JudgeCfg), C.POINTER(Judge), C.POINTER(FollowCfg),
+                                        C.POINTER(Follow)]
+    lib.pp_rollout_reactive.restype = C.c_int32
     lib.pp_synth_traffic.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.POINTER(SceneBatch),
                                      C.POINTER(Traffic), C.c_int32, C.c_void_p]
     lib.pp_synth_traffic.restype = C.c_int32
@@ -545,6 +575,75 @@ def rollout_judged(m, scenes, traffic, prm, result, judge, n_frames, consume=3, 
     _check(lib.pp_rollout_judged(m.handle, C.byref(b), C.byref(T), C.byref(prm), C.byref(rc), C.byref(R),
                                  C.byref(L) if L is not None else None, device, stream, C.byref(cfg),
                                  C.byref(J)), "pp_rollout_judged")
+
+
+def default_follow_cfg(**over) -> FollowCfg:
+    """pp_follow_cfg_default, with fields overridden by keyword."""
+    c = FollowCfg()
+    lib.pp_follow_cfg_default(C.byref(c))
+    for k, v in over.items():
+        if k not in dict(FollowCfg._fields_):
+            raise KeyError(k)
+        setattr(c, k, v)
+    return c
+
+
+def alloc_follow(S, n=12, xp="numpy", device=None):
+    """Zero-filled follow state of S scenes x n cars (every scene a fresh episode)."""
+    if xp == "numpy":
+        mk = lambda sh, dt: np.zeros(sh, dt)
+    else:
+        import torch
+        tdt = {"f8": torch.float64, "i4": torch.int32}
+        mk = lambda sh, dt: torch.zeros(sh, dtype=tdt[dt], device=device)
+    return {k: mk((n, S) if per_car else (S,), dt) for k, dt, per_car in FOLLOW_FIELDS}
+
+
+def follow_struct(f) -> Follow:
+    F = Follow()
+    for k, _, _ in FOLLOW_FIELDS:
+        setattr(F, k, _ptr(f[k]))
+    return F
+
+
+def follow_to_numpy(f):
+    return {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in f.items()}
+
+
+def traffic_follow(m, scenes, traffic, follow, consume=3, cfg=None, host=None, device=0, stream=None):
+    """pp_traffic_follow / pp_traffic_follow_host: the car-following update of one frame from the
+    pre-frame scenes and traffic; traffic["speed"] and `follow` are updated in place. host=None picks
+    the host twin when the arrays are numpy."""
+    if host is None:
+        host = isinstance(scenes["ego_x"], np.ndarray)
+    cfg = cfg if cfg is not None else default_follow_cfg()
+    assert follow["desired"].shape[0] >= int(traffic["n_cars"]), "follow state holds fewer cars than the traffic"
+    b, T, F = scene_struct(scenes), traffic_struct(traffic), follow_struct(follow)
+    if host:
+        _check(lib.pp_traffic_follow_host(m.handle, C.byref(b), C.byref(T), consume, C.byref(cfg), C.byref(F)),
+               "pp_traffic_follow_host")
+    else:
+        _check(lib.pp_traffic_follow(m.handle, C.byref(b), C.byref(T), consume, C.byref(cfg), C.byref(F), device,
+                                     stream), "pp_traffic_follow")
+
+
+def rollout_reactive(m, scenes, traffic, prm, result, follow, n_frames, consume=3, sensor_range=300.0, log=None,
+                     judge=None, jcfg=None, fcfg=None, device=0, stream=None):
+    """pp_rollout_reactive: rollout() whose traffic follows the vehicle ahead (follow state updated in
+    place), judged on every frame when `judge` is given."""
+    assert follow["desired"].shape[0] >= int(traffic["n_cars"]), "follow state holds fewer cars than the traffic"
+    b, T, R, F = scene_struct(scenes), traffic_struct(traffic), result_struct(result), follow_struct(follow)
+    rc = RolloutCfg(n_frames, consume, float(sensor_range))
+    fcfg = fcfg if fcfg is not None else default_follow_cfg()
+    J = judge_struct(judge) if judge is not None else None
+    if judge is not None and jcfg is None:
+        jcfg = default_judge_cfg()
+    L = log_struct(log) if log is not None else None
+    _check(lib.pp_rollout_reactive(m.handle, C.byref(b), C.byref(T), C.byref(prm), C.byref(rc), C.byref(R),
+                                   C.byref(L) if L is not None else None, device, stream,
+                                   C.byref(jcfg) if jcfg is not None else None,
+                                   C.byref(J) if J is not None else None, C.byref(fcfg), C.byref(F)),
+           "pp_rollout_reactive")
 
 
 def plan_reset(m, device=0):

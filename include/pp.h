@@ -371,6 +371,73 @@ int32_t pp_rollout_judged(pp_map* m, pp_scene_batch* telemetry, pp_traffic* traf
                           pp_rollout_log* log, int32_t device, void* hip_stream,
                           const pp_judge_cfg* jcfg, pp_judge* state);
 
+/* ---- reactive traffic: every car follows the vehicle ahead of it in its lane ------------------- */
+/* pp_rollout's traffic keeps its speed for ever and drives through the ego and through other cars.
+ * Here each car follows the nearest vehicle ahead of it in its lane (another car, or the ego where
+ * it stands within lateral_reach of that lane's centre) by the Intelligent Driver Model. One call
+ * updates traffic.speed in place for one frame of `consume` steps (dt = consume 0.02 s) from the
+ * PRE-FRAME state; positions are not touched (the simulator moves the cars). The definitions are
+ * THIS LIBRARY'S OWN (DESIGN.md "Reactive traffic" states them in full); the reference has no
+ * simulator and nothing is compared with it. In short, with v a car's speed, v0 its desired speed,
+ * vl its leader's speed and g the net gap along the lane (centre gap minus the half lengths):
+ *   free = 1 - (v / v0)^4
+ *   s*   = min_gap + max(0, v time_headway + v (v - vl) / (2 sqrt(max_acc comfort_brake)))
+ *   a    = max_acc (free - (s* / max(g, gap_floor))^2), or max_acc free with no leader within horizon
+ *   v'   = min(max(v + max(a, -max_brake) dt, 0), v0)
+ * Every v' comes from the pre-frame speeds of all cars. A car with v0 <= 0 (parked) is left alone. */
+typedef struct pp_follow_cfg {
+    double  max_acc;               /* 2.0 m/s^2: the acceleration on a free road from rest         */
+    double  comfort_brake;         /* 3.0 m/s^2: the deceleration the model approaches a leader by */
+    double  max_brake;             /* 8.0 m/s^2: a is never below -max_brake                       */
+    double  time_headway;          /* 1.2 s                                                        */
+    double  min_gap;               /* 2.0 m: the net gap kept at standstill                        */
+    double  gap_floor;             /* 0.5 m: net gaps below this (overlapping cars) count as this  */
+    double  horizon;               /* 150 m: a vehicle with a net gap beyond this is no leader     */
+    double  car_length;            /* 4.5 m                                                        */
+    double  ego_length;            /* 4.5 m                                                        */
+    double  lateral_reach;         /* 2.0 m: the ego occupies a lane whose centre is this near     */
+    int32_t react_to_ego;          /* 1: the ego is a leader candidate; 0: the cars do not see it  */
+    int32_t _pad;
+} pp_follow_cfg;                   /* max_acc, comfort_brake, max_brake, gap_floor > 0; horizon,
+                                      lengths and lateral_reach >= 0                               */
+
+/* Follow state of a batch (SoA, caller owned; device resident for pp_traffic_follow and
+ * pp_rollout_reactive, host memory for pp_traffic_follow_host), S = the telemetry's n_scenes, per-car
+ * arrays [j * S + s] for j < traffic.n_cars. A scene whose started[s] is 0 on entry starts a fresh
+ * episode: its cars' desired speeds are captured from traffic.speed and every other field of it is
+ * written by the call, so a zero-filled state is a valid start and a state is reused by zeroing
+ * `started` alone. */
+typedef struct pp_follow {
+    int32_t* started;              /* 0 = fresh episode; set to 1 by the call                      */
+    int32_t* ego_seg;              /* carried: lane-centre segment nearest to the ego + 1, 0: none */
+    double*  desired;              /* [j * S + s] v0, captured on the fresh call                   */
+    double*  next_speed;           /* [j * S + s] staging (the new speeds before they are written) */
+    int32_t* leader;               /* [j * S + s] record: -1 none, n_cars the ego, else the car    */
+    double*  gap;                  /* [j * S + s] record: the net gap g, +inf with no leader       */
+} pp_follow;
+
+void    pp_follow_cfg_default(pp_follow_cfg* c);
+/* Updates traffic->speed for ONE frame from the pre-frame state: `telemetry` (ego_x, ego_y,
+ * ego_speed_mph are read) and `traffic` (lane, seg, t, speed) as they are before the simulator
+ * moves them. For callers that run their own loop around pp_eval: call it before pp_judge_frame and
+ * before moving the traffic, so that the judge and the move use the speeds of this frame. Writes
+ * traffic->speed and `state` only. lane and seg are trusted as pp_rollout trusts them. Device
+ * pointers; asynchronous on hip_stream. */
+int32_t pp_traffic_follow(pp_map* m, const pp_scene_batch* telemetry, pp_traffic* traffic, int32_t consume,
+                          const pp_follow_cfg* cfg, pp_follow* state, int32_t device, void* hip_stream);
+/* The same on the host (host pointers; the same arithmetic, bit for bit). */
+int32_t pp_traffic_follow_host(const pp_map* m, const pp_scene_batch* telemetry, pp_traffic* traffic,
+                               int32_t consume, const pp_follow_cfg* cfg, pp_follow* state);
+/* pp_rollout with reactive traffic: per frame pp_eval, the follow update, the judge (only when
+ * jstate is not NULL; jcfg is then required), then the simulator, on the one stream. The judge
+ * advances the cars over the frame's steps by the speeds the simulator then moves them by, and the
+ * simulator reports those speeds in the next telemetry. */
+int32_t pp_rollout_reactive(pp_map* m, pp_scene_batch* telemetry, pp_traffic* traffic,
+                            const pp_params* prm, const pp_rollout_cfg* cfg, pp_result* result,
+                            pp_rollout_log* log, int32_t device, void* hip_stream,
+                            const pp_judge_cfg* jcfg, pp_judge* jstate,
+                            const pp_follow_cfg* fcfg, pp_follow* fstate);
+
 /* Rollout start state: writes the synthetic scenes of pp_synth_scenes (same seed and indices)
  * into `telemetry` and their traffic into `out` (n_cars = 12): car j starts exactly where the
  * scene reports it, on its lane with its lateral offset and speed. Empties the car table of
