@@ -55,7 +55,7 @@ struct MapV {
     // Map::project_speed computes (src/main.cpp:339) and its correctly rounded reciprocal; null:
     // computed in place
     const double2* wseg = nullptr;
-    // the approach table (pp_eval.hip build_atab): kAtabD doubles per lane segment b, used where
+    // the approach table (pp_host_map.h build_atab): kAtabD doubles per lane segment b, used where
     // atab_on (k_prep: in LDS when the map is, so that its loads are LDS loads)
     const double* atab = nullptr;
     bool atab_on = false;

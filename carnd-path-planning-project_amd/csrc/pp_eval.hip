@@ -13,6 +13,11 @@
 //   K3 k_winner  comfort mode: per-scene argmin + re-run of the winning candidate with outputs.
 //                (reference mode: the winner is known before the loop; k_cand's first wave of
 //                each block runs the winners and writes next_x/next_y)
+//
+// Contents, in order: diagnostic-build hooks; the output frame, winner record and map staging;
+// K0/K1 scene preparation; K2 candidates; K3/K4 output; the fused small-batch and frame kernels;
+// rollout, synthesis, map and libm kernels; then the host side, which lives in the headers
+// included at the end (pp_host_map.h, pp_launch.h, pp_api.h, pp_api_rollout.h, pp_api_frame.h).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -169,7 +174,7 @@ __device__ __forceinline__ void st_xy(double* p, double x, double y) {
 // launch shape that writes the reference decision's next_x/next_y (k_emit, the fused small-batch
 // kernels) or a winner's (k_winner) calls these same functions, so their outputs stay bit-identical
 // to each other (and within ~1e-11 m of the reference after a turn, equal to it before the first
-// one). k_cand's all-paths mode has a cheaper variant below (frame_pt_fma, frame_turn_at).
+// one). k_cand's all-paths mode has a cheaper variant below (frame_step, turn_narrow).
 struct OutFrame { double cx, cy, ca, sa; };   // centre, cos and sin of the frame's heading
 // a point: the reference's own operations (src/main.cpp:1033-1036), unfused: until a path's first
 // curvature adjustment its points carry the reference's bits, and in a closed loop those first
@@ -245,24 +250,9 @@ __device__ __forceinline__ void turn_sincos(double r, double& s, double& c) {
 
 // k_cand's all-paths mode (output mode 4): the same output frame, cheaper. Every candidate writes
 // its path there, so the point transform runs on every lane-step and a turn on about half of all
-// wave-steps (for one lane in ten): each point is two fused multiply-adds per coordinate
-// (frame_pt_fma); the loop keeps the last output point o, so a turn sets the centre from it — c = o -
-// R' p, the current point keeps its output — instead of rotating the old centre about o; the turn
-// angle's reciprocal takes one Newton step. ~1e-13 m from the shared turn (frame_turn); the paths' tolerance is 1e-6 m, and
-// no decision and no closed loop reads these points (the reference decision's next_x/next_y and
-// every fed-back path come from frame_turn / k_emit).
-__device__ __forceinline__ void frame_turn_at(OutFrame& f, double px, double py, double ox, double oy,
-                                              double cr, double sr) {
-    const double nca = __builtin_fma(f.ca, cr, -(f.sa * sr)), nsa = __builtin_fma(f.sa, cr, f.ca * sr);
-    f.ca = nca;
-    f.sa = nsa;
-    f.cx = ox - __builtin_fma(nca, px, -(nsa * py));
-    f.cy = oy - __builtin_fma(nsa, px, nca * py);
-}
-__device__ __forceinline__ void frame_pt_fma(const OutFrame& f, double px, double py, double& ox, double& oy) {
-    ox = __builtin_fma(px, f.ca, __builtin_fma(-py, f.sa, f.cx));
-    oy = __builtin_fma(px, f.sa, __builtin_fma(py, f.ca, f.cy));
-}
+// wave-steps (for one lane in ten); the turn angle's reciprocal takes one Newton step. The paths'
+// tolerance is 1e-6 m, and no decision and no closed loop reads these points (the reference
+// decision's next_x/next_y and every fed-back path come from frame_turn / k_emit).
 __device__ __forceinline__ double turn_angle_fast(double nc, double speed, double adiff) {
     double r = __builtin_amdgcn_rcp(speed);
     r = __builtin_fma(__builtin_fma(-speed, r, 1.0), r, r);
@@ -270,34 +260,18 @@ __device__ __forceinline__ double turn_angle_fast(double nc, double speed, doubl
     if (adiff < 0) nad = -nad;
     return nad - adiff;
 }
-// Round 5 (PP_PATHS_INC, default on): k_cand's all-paths frame without a centre. The reference's
-// turn rotates the centre about the current output point tp (src/main.cpp:995-1004), so tp stays
-// where it is and every later point is o_{k+1} = o_k + R_{k+1} (p_{k+1} - p_k): the loop keeps the
-// last output point o and the heading (ca, sa) only, and a point is o plus the rotated local step
-// (frame_step: the same four fused multiply-adds as frame_pt_fma). A narrow turn (the step's
-// angle came from asin(u_prev x u): |adiff| <= 0.0709) rotates by rot = nad - adiff, i.e. by
-// R(nad) R(-adiff), and (cos, sin)(adiff) are the step's own unit-vector products (dt, cr): only
-// sin/cos of |nad| < |adiff| are left, short Taylor polynomials (sincos_small). The points differ
+// Round 5: k_cand's all-paths frame without a centre. The reference's turn rotates the centre
+// about the current output point tp (src/main.cpp:995-1004), so tp stays where it is and every
+// later point is o_{k+1} = o_k + R_{k+1} (p_{k+1} - p_k): the loop keeps the last output point o
+// and the heading (ca, sa) only, and a point is o plus the rotated local step (frame_step: two
+// fused multiply-adds per coordinate). A narrow turn (the step's angle came from asin(u_prev x u):
+// |adiff| <= 0.0709) rotates by rot = nad - adiff, i.e. by R(nad) R(-adiff), and (cos, sin)(adiff)
+// are the step's own unit-vector products (dt, cr): only sin/cos of |nad| < |adiff| are left,
+// short Taylor polynomials (sincos_small). The points differ
 // from the reference's by rounding only (the summed steps: ~1e-13 m over a 100-point path); no
 // decision reads them.
-#ifndef PP_PATHS_INC
-#define PP_PATHS_INC 1
-#endif
-#ifndef PP_RCP1
-#define PP_RCP1 0
-#endif
-#ifndef PP_DT_NARROW
-#define PP_DT_NARROW 0
-#endif
-
-// a narrow step turn (asin_small's domain): u_prev . u > 0 and |u_prev x u| <= kStepSinMax; for unit
-// vectors (to a few ulps) the same as u_prev . u >= sqrt(1 - kStepSinMax^2) (PP_DT_NARROW: one
-// compare; |cr| then exceeds kStepSinMax by < 1e-14 at most, where the series is as accurate)
-#if PP_DT_NARROW
-#define PP_NARROW(dt, cr) ((dt) >= 0.99749053128338025)
-#else
+// a narrow step turn (asin_small's domain): u_prev . u > 0 and |u_prev x u| <= kStepSinMax
 #define PP_NARROW(dt, cr) ((dt) > 0 && fabs(cr) <= ppm::kStepSinMax)
-#endif
 __device__ __forceinline__ void frame_step(double ca, double sa, double dpx, double dpy, double& ox, double& oy) {
     ox = __builtin_fma(dpx, ca, __builtin_fma(-dpy, sa, ox));
     oy = __builtin_fma(dpx, sa, __builtin_fma(dpy, ca, oy));
@@ -332,26 +306,11 @@ __device__ __forceinline__ void turn_narrow(double& ca, double& sa, double nc, d
     frame_rot(ca, sa, __builtin_fma(cn, dt, sn * cr), __builtin_fma(sn, dt, -(cn * cr)));
 }
 // Tuning constants (each measured against its alternatives):
-#ifndef PP_EMIT_CHUNK
-#define PP_EMIT_CHUNK 4
-#endif
-constexpr int kEmitChunk = PP_EMIT_CHUNK;   // emit_scene_pre (small batches): recorded steps loaded together per lane
+constexpr int kEmitChunk = 4;      // emit_scene_pre (small batches): recorded steps loaded together per lane
 constexpr int kEmitRows = 8;       // k_emit (large batches, emit_scene_rows): output rows per load round
 constexpr int kWalkPf = 4;         // segments of the control-point walk loaded ahead (get_lane_pos_fwd)
 constexpr int kPrepWaves = 3;      // k_prep waves per SIMD (kW4: 4)
-#ifndef PP_CAND_WAVES
-#define PP_CAND_WAVES 4
-#endif
-#ifndef PP_CAND_WAVES2
-#define PP_CAND_WAVES2 PP_CAND_WAVES    // the all-paths instantiation k_cand<., 2>
-#endif
-#ifndef PP_UNROLL2
-#define PP_UNROLL2 1
-#endif
-#ifndef PP_ASIN_S
-#define PP_ASIN_S 0
-#endif
-constexpr int kCandWaves = PP_CAND_WAVES;   // k_cand waves per SIMD (<= 128 VGPRs)
+constexpr int kCandWaves = 4;      // k_cand waves per SIMD (<= 128 VGPRs), every instantiation
 // Winner record (k_cand -> k_emit), room = N - K steps of scene s, rstride = room S: point-major
 // arrays, pos_x at rec[g S + s], pos_y at rec[rstride + g S + s], the rotation of an adjusted step
 // at rec[2 rstride + g S + s] (every address of scene s is = s mod S: a wave's accesses coalesce)
@@ -897,11 +856,7 @@ __device__ __forceinline__ void car_noise(const pp_params& P, int64_t s, int dra
                                           double& cy, double& cvx, double& cvy) {
     const uint64_t gs = (uint64_t)(P.noise_first_scene + s);
     double g[4];
-#ifndef PP_G4
-#define PP_G4 1
-#endif
-    if (PP_G4) ppsynth::mc_gauss4(P.noise_seed, gs, draw, row, g);      // (mc_gauss q = 0..3)
-    else for (int q = 0; q < 4; q++) g[q] = ppsynth::mc_gauss(P.noise_seed, gs, draw, row, q);
+    ppsynth::mc_gauss4(P.noise_seed, gs, draw, row, g);      // (mc_gauss q = 0..3)
     cx += P.noise_pos_sigma * g[0];
     cy += P.noise_pos_sigma * g[1];
     cvx += P.noise_vel_sigma * g[2];
@@ -909,21 +864,16 @@ __device__ __forceinline__ void car_noise(const pp_params& P, int64_t s, int dra
 }
 
 // kW4: the 4-waves-per-SIMD instantiation (<= 128 VGPRs): for batches whose wave count fills
-// whole rounds of 4 waves per SIMD better than of 3 (prep_w4 in pp_eval)
-#ifndef PP_SORT_DMAX
-#define PP_SORT_DMAX 16          // k_prep sorts a scene's rows nearest first below this many draws
-#endif
-#ifndef PP_SORT_K0
-#define PP_SORT_K0 0             // 1: k_sort_cars by default (PP_DBG_SORT_CARS switches it per call)
-#endif
-// K0 (round 6, PP_SORT_K0): each scene's cars in k_prep's visiting order, visit-major.
+// whole rounds of 4 waves per SIMD better than of 3 (prep_w4 in pp_launch.h)
+constexpr int kSortDmax = 16;    // k_prep sorts a scene's rows nearest first below this many draws
+// K0 (round 6; PP_DBG_SORT_CARS selects it per call): each scene's cars in k_prep's visiting order, visit-major.
 // k_prep visits a scene's rows nearest first (below), and read them in that order straight from the
 // batch's row-major arrays: a wave's load of visit k gathers 64 scenes' rows from up to 12 rows,
 // each cache line partly used and fetched again at later visits (FETCH ~7x the scene record,
 // DESIGN.md §4). k_sort_cars computes the same order (the same keys, the same network, the same
 // identity-order rules) and writes the rows permuted into visit-major arrays x[k][s], ... through a
 // per-lane LDS column, so k_prep's visit k reads 64 consecutive values per field. Only for batches
-// without a car table, fewer than PP_SORT_DMAX draws and at most 16 rows per scene (the host's
+// without a car table, fewer than kSortDmax draws and at most 16 rows per scene (the host's
 // condition); the values are copies, so k_prep's results are the same bits.
 struct SortedCars {
     double *x, *y, *vx, *vy;      // [k][S], k < rows: the k-th visited row's fields
@@ -1011,10 +961,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kW4 ? 4 : k
 #endif
     // the approach table: in LDS after the map (16-B aligned) in k_prep<true, false> (the host
     // sizes the launch for it, or passes none), else in global memory
-#ifndef PP_ATAB_LDS
-#define PP_ATAB_LDS 1
-#endif
-    constexpr bool kAtabL = kLdsMap && !kW4 && PP_ATAB_LDS;
+    constexpr bool kAtabL = kLdsMap && !kW4;
     double* satab = smap + ((kMapArrays * n + 1) & ~1);
     if (kLdsMap) {
         stage_map(smap, mg.buf, kMapArrays * n);
@@ -1076,7 +1023,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kW4 ? 4 : k
 #ifdef PP_ABL_NOSORT
     if (false) {
 #else
-    if (!k0 && !tab && iters > 1 && iters <= 16 && D < PP_SORT_DMAX) {
+    if (!k0 && !tab && iters > 1 && iters <= 16 && D < kSortDmax) {
 #endif
         uint32_t key[16];
         bool neg = false;
@@ -1206,11 +1153,6 @@ __device__ __forceinline__ void prep_grp_body(MapG mg, pp_scene_batch in, pp_par
     prep_grp_eval<G>(m, in, P, pv, info, out_status, gb, v, r);
 }
 
-// the grouped K1's planner pass: the group's cars at once (PlanAcc::add_group), or one at a time
-#ifndef PP_GROUP_PASS
-#define PP_GROUP_PASS 1
-#endif
-constexpr bool kGroupPass = PP_GROUP_PASS != 0;
 // One evaluation v by the G lanes of a group (this one is lane r); every lane of the group runs it
 template <int G>
 __device__ __forceinline__ void prep_grp_eval(const MapV& m, const pp_scene_batch& in, const pp_params& P,
@@ -1336,7 +1278,8 @@ __device__ __forceinline__ void prep_grp_eval(const MapV& m, const pp_scene_batc
             }
         }
         PP_TRACE_K1(3);
-        if (kGroupPass && grp_or<G>((okl & 1) && id == -1 ? 1u : 0u) == 0u) {
+        // the planner pass: the group's cars at once (PlanAcc::add_group), or one at a time
+        if (grp_or<G>((okl & 1) && id == -1 ? 1u : 0u) == 0u) {
             a.add_group<G>(P, e, T_in, (okl & 1) != 0, j, id, cs, cd, okl >> 1, cvs, cvd);
         } else {
             const int nq = iters - j0 < G ? iters - j0 : G;
@@ -1717,7 +1660,7 @@ struct CandRes { double acc_sum, travelled; int ng; uint32_t flags; uint64_t adj
 // transform (centre, angle); the local path (pos_x, pos_y, arg, speed, angles) that the cost reads
 // never depends on it, so a cost-only lane skips the transform, its sin/cos and the stores.
 //   kOutMode 0: cost only;  2: every lane produces points;  4: the same with k_cand's cheaper
-//   output-frame turn (frame_turn_at);  3: lanes with out_on RECORD their local path (pos after each step, rotation angle of each
+//   output frame (frame_step, turn_narrow);  3: lanes with out_on RECORD their local path (pos after each step, rotation angle of each
 //   curvature adjustment + a bitmask of the adjusted steps) for k_emit, which replays the
 //   transform — the expensive sin/cos of the adjustments leaves the candidate loop entirely.
 // Point g goes to wx[g*ws], wy[g*ws] (if wx) and px[g*ps], px[g*ps+1] (if px); in mode 3 the record
@@ -1789,14 +1732,8 @@ __device__ CandRes run_candidate(const pp_params& P, const Slot& sl, double cx, 
     double arg = 0, prev_speed = sc.start;
     double uxp = 1.0, uyp = 0.0;     // previous step direction (angle 0: the local frame's x axis)
     // 1 / (target - start) for SpeedController::override_speed (constant over the walk)
-#if PP_RCP1
-    // (both reciprocals feed only Markstein-corrected quotients: ppm::rcp_nr1 is enough)
-    const double rds = ppm::rcp_nr1(sc.target - sc.start);
-    double rtt = ppm::rcp_nr1(sc.ttime);
-#else
     const double rds = ppm::rcp_nr(sc.target - sc.start);
     double rtt = ppm::rcp_nr(sc.ttime);
-#endif
     PP_DIAGC(20, true);     // (waves entering the loop)
 #ifdef PP_LIMCENSUS
     double ref_pa = 0;      // the reference's prev_angle (src/main.cpp:906): the previous step's atan2
@@ -1804,7 +1741,7 @@ __device__ CandRes run_candidate(const pp_params& P, const Slot& sl, double cx, 
     // the divisions by 50 and by the ramp time: reciprocal + correction (k_cand<false>: unchecked)
 #define PP_DIV50(v) (kLarge ? ppm::div_rcp(v, 50.0, 0.02) : ppm::div50_nc(v))
     // one step of the loop (src/main.cpp:911-1040): (uxp, uyp) the previous step's unit direction,
-    // prev_speed its speed; the step's own go to (uxn, uyn, psn). PP_UNROLL2 runs two steps per
+    // prev_speed its speed; the step's own go to (uxn, uyn, psn). The loop runs two steps per
     // iteration with the two register sets alternating (no copies at the back edge)
     auto step = [&](const double uxp, const double uyp, const double prev_speed, double& uxn, double& uyn,
                     double& psn) __attribute__((always_inline)) {
@@ -1890,7 +1827,7 @@ __device__ CandRes run_candidate(const pp_params& P, const Slot& sl, double cx, 
             PP_DIAGC(9, !(dt > 0));
             if (__builtin_expect(PP_NARROW(dt, cr), 1)) {
                 PP_REGION("asin");
-                adiff = (((PP_ASIN_S == 2 ? ppm::asin_small_b(cr) : PP_ASIN_S ? ppm::asin_small_s(cr) : ppm::asin_small(cr)) + 3 * kPi) - 2 * kPi) - kPi;
+                adiff = ((ppm::asin_small(cr) + 3 * kPi) - 2 * kPi) - kPi;
             } else {
                 PP_REGION("wide");
                 // cr, dt: components of unit vectors (finite, never both zero; NaN propagates)
@@ -1938,7 +1875,7 @@ __device__ CandRes run_candidate(const pp_params& P, const Slot& sl, double cx, 
                     sc_override_r<kLarge>(sc, cur_t, ns, rds);
                     speed = ns;
                     sc.ttime += 0.02;
-                    rtt = PP_RCP1 ? ppm::rcp_nr1(sc.ttime) : ppm::rcp_nr(sc.ttime);
+                    rtt = ppm::rcp_nr(sc.ttime);
                     dstep = PP_DIV50(speed);
                     acc = na;
                     R.flags |= PP_ST_ACC_OVERRIDE;
@@ -1958,7 +1895,6 @@ __device__ CandRes run_candidate(const pp_params& P, const Slot& sl, double cx, 
                         turn_sincos<kLarge>(turn_angle<kLarge>(nc, speed, adiff), sr, cr);
                         frame_turn(F, pos_x, pos_y, cr, sr);
                     } else if (kOutMode == 4) {
-    #if PP_PATHS_INC
                         PP_DIAGC(19, !(!kLarge && PP_NARROW(dt, cr)));
                         PP_DIAGC(23, !kLarge && PP_NARROW(dt, cr));
                         if (!kLarge && PP_NARROW(dt, cr)) {
@@ -1971,11 +1907,6 @@ __device__ CandRes run_candidate(const pp_params& P, const Slot& sl, double cx, 
                                                        : turn_angle_fast(nc, speed, adiff), srr, crr);
                             frame_rot(F.ca, F.sa, crr, srr);
                         }
-    #else
-                        double cr, sr;
-                        turn_sincos<kLarge>(turn_angle_fast(nc, speed, adiff), sr, cr);
-                        frame_turn_at(F, pos_x, pos_y, opx, opy, cr, sr);
-    #endif
                     }
                     if (kOutMode == 3 && kRec) {
                         // the turn angle for k_emit's replay of the output frame
@@ -2012,11 +1943,7 @@ __device__ CandRes run_candidate(const pp_params& P, const Slot& sl, double cx, 
                 PP_REGION("out");
                 PP_DIAGC(22, wx != nullptr);
                 double ox, oy;
-    #if PP_PATHS_INC
                 if (kOutMode == 4) { ox = opx; oy = opy; frame_step(F.ca, F.sa, sp_step, dpy, ox, oy); }
-    #else
-                if (kOutMode == 4) frame_pt_fma(F, pos_x, pos_y, ox, oy);
-    #endif
                 else frame_pt(F, pos_x, pos_y, ox, oy);
                 if (wx && PP_CHKP(wx + ng * ws, nx, nnext, 1) && PP_CHKP(wy + ng * ws, ny, nnext, 2)) { PP_REGION("outw"); wx[ng * ws] = ox; wy[ng * ws] = oy; }
                 PP_REGION("out2");
@@ -2030,22 +1957,12 @@ __device__ CandRes run_candidate(const pp_params& P, const Slot& sl, double cx, 
             R.acc_sum += acc + eff_c;
             R.travelled += dstep;
         };
-#if PP_UNROLL2
     double uxq = 0, uyq = 0, psq = 0;
     while (arg < 50 && ng < room) {
         step(uxp, uyp, prev_speed, uxq, uyq, psq);
         if (!(arg < 50 && ng < room)) break;
         step(uxq, uyq, psq, uxp, uyp, prev_speed);
-#if PP_UNROLL2 > 1
-        if (!(arg < 50 && ng < room)) break;
-        step(uxp, uyp, prev_speed, uxq, uyq, psq);
-        if (!(arg < 50 && ng < room)) break;
-        step(uxq, uyq, psq, uxp, uyp, prev_speed);
-#endif
     }
-#else
-    while (arg < 50 && ng < room) step(uxp, uyp, prev_speed, uxp, uyp, prev_speed);
-#endif
     PP_REGION("end");
     R.ng = ng;
     return R;
@@ -2153,9 +2070,6 @@ __device__ __forceinline__ void emit_scene_pre(const pp_scene_batch& in, const p
 // single-frame and small-batch step, whose time is the winners' serial chain)
 // kPreA: the block's (single) scene has its fast-path spline slots built already (k_plan_frame's
 // second wave builds them while the first runs K1): phase A is skipped
-#ifndef PP_WSLOT
-#define PP_WSLOT 1            // 0: k_winner makes the decision and builds the winner's spline (A/B)
-#endif
 // k_winner's blocks and spline slots (kWinKnots = 9 previous + 6 control points, the real maximum)
 constexpr int kWinBlock = 64;
 constexpr int kWinKnots = 15;
@@ -2498,7 +2412,7 @@ __device__ __forceinline__ void cand_group(const MapG& mg, const pp_scene_batch&
 // are block-uniform; a barrier separates consecutive groups' use of the block's LDS). Each group
 // clears its bit after use, so the bitmap is all zero again for the next pp_eval.
 template <bool kSlow, int kMode>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kMode == 2 ? PP_CAND_WAVES2 : kCandWaves))) void k_cand(MapG mg, pp_scene_batch in, pp_params P, PrepV pv,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kCandWaves))) void k_cand(MapG mg, pp_scene_batch in, pp_params P, PrepV pv,
                                               pp_result out, int SPB, int BPS, double* rec, uint64_t* adjm,
                                               uint32_t* gbits, int64_t ngroups, const uint32_t* glist,
                                               const uint32_t* gcount, int64_t g0, double* wslot) {
@@ -2839,16 +2753,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
 // phase A reading the same LDS map. The prep record goes through global memory inside the block
 // (written, barrier, read by the same workgroup). No kernel boundary is left in the step.
 // ------------------------------------------------------------------------------------------------
-#ifndef PP_STEP_EMIT
-#define PP_STEP_EMIT 2
-#endif
 // the winners' output in the one-launch step (cand_group kEmitIn): inline (2) or replayed (1)
-constexpr int kStepEmit = PP_STEP_EMIT;
-// the one-launch step with phase A beside K1 (wave_step_body) where the blocks allow it
-#ifndef PP_STEP_WAVES
-#define PP_STEP_WAVES 1
-#endif
-constexpr bool kStepWaves = PP_STEP_WAVES != 0;
+constexpr int kStepEmit = 2;
 // doubles of k_cand's LDS for SPB scenes (cand_geom_lds, host), rounded up
 __host__ __device__ constexpr int cand_lds_doubles(int spb) {
     return (int)(((sizeof(double) * 5 * kKP * (NL * spb) + sizeof(int) * 4 * (NL * spb) + sizeof(uint32_t) * 2 * spb + 7) / 8 * 8 +
@@ -2908,10 +2814,6 @@ __device__ __forceinline__ void step_small_body(MapG mg, const pp_scene_batch& i
 constexpr int kStepWaveSpb = 8;
 constexpr int kGeoD = 17;           // (the last: the heading)
 static_assert(9 + NL <= kGeoD - 1, "geometry record");
-#ifndef PP_POSE_BY_WAVE
-#define PP_POSE_BY_WAVE 1
-#endif
-constexpr bool kPoseByWave = PP_POSE_BY_WAVE != 0;
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -2999,7 +2901,7 @@ __device__ __forceinline__ void wave_step_body(MapG mg, const pp_scene_batch& in
     const int tid = (int)threadIdx.x;
     if (tid < kThreads / 2) {                     // K1: scene s0 + tid / 16 by 16 lanes
         const int q = tid / 16;
-        const GroupBits nobits = {nullptr, SPB, 1, nullptr, nullptr, kPoseByWave ? 1 : 0};
+        const GroupBits nobits = {nullptr, SPB, 1, nullptr, nullptr, 1};
         if (q < nsc) prep_grp_eval<16>(m, in, P, pv, out.info, out.status, nobits, s0 + q, tid % 16);
     } else {
         wave_phase_a(m, in, P, pv, SPB, csm, geo, s0, nsc, (tid - kThreads / 2) / 64, tid % 64);
@@ -3010,7 +2912,7 @@ __device__ __forceinline__ void wave_step_body(MapG mg, const pp_scene_batch& in
     __syncthreads();
     // the heading's kLimSlow bit (recorded by the phase-A waves), before cand_group's first read
     // of lim_mask (behind its first barrier)
-    if (kPoseByWave && tid < nsc && !(fabs(geo[tid * kGeoD + kGeoD - 1]) <= kSlowAngle))
+    if (tid < nsc && !(fabs(geo[tid * kGeoD + kGeoD - 1]) <= kSlowAngle))
         pv.lim_mask[s0 + tid] |= kLimSlow;
 #ifdef PP_TRACE
     if (blockIdx.x == 0 && tid == 0) trace_at(kTraceK1 - 1, 1);
@@ -3352,2018 +3254,11 @@ __global__ __launch_bounds__(256) void k_synth(ppsynth::LaneTables T, uint64_t s
 }
 
 // ================================================================================================
-// host side: map, per-device state, C-ABI
+// host side, in the headers below (this file keeps the kernels; one translation unit, so the
+// launches see them)
 // ================================================================================================
-namespace {
-
-constexpr int kMaxDev = 16;
-constexpr int kMaxWaypoints = 1 << 24;
-constexpr int kPrepD = 12 + 4 * NL;   // doubles per scene in PrepV (see prep_bind)
-constexpr int kPrepI = 7;
-
-// pp_eval's device workspaces, one set per HIP stream: evaluations on different streams never
-// share intermediate buffers, and evaluations on one stream are ordered by it. A buffer is grown
-// only after that stream has drained (it is the only stream using it).
-// the split of shard-sized batches: parts (streams) per call, at most kSplitMax (split_parts)
-constexpr int kSplitMax = 4;
-// parts per call: a batch beyond kSplitMaxScenes runs as chunks of parts, part t on stream t % streams
-// (split_chunks); each part has its own flagged-group count word and 4 timing-event slots
-constexpr int kPartMax = 16;
-#ifndef PP_SPLIT_PARTS
-#define PP_SPLIT_PARTS 0      // 0: by batch size (split_parts); 2..4 forced (A/B builds)
-#endif
-struct StreamWS {
-    void* ws = nullptr;           // prep workspace (per evaluation: scene x draw)
-    int64_t ws_cap = 0;
-    void* rec = nullptr;          // reference-mode winner record (per scene)
-    int64_t rec_cap = 0;
-    uint32_t* gbits = nullptr;    // k_cand groups holding a kLimSlow scene (bitmap; all zero between calls)
-    int64_t gbits_cap = 0;        // words
-    void* srt = nullptr;          // k_sort_cars' visit-major rows (SortedCars)
-    size_t srt_cap = 0;           // bytes
-    hipStream_t st2[kSplitMax - 1] = {};   // the split's other streams (shard-sized batches)
-    hipEvent_t fork = nullptr, join[kSplitMax - 1] = {};
-};
-struct DevState {
-    bool init = false;
-    double* map = nullptr;        // kMapArrays * n
-    uint2* wgrid = nullptr;       // the closest-waypoint cell table (pp_map::wgrid)
-    double2* wseg = nullptr;      // reference segment lengths and reciprocals (pp_map::wseg)
-    double* atab = nullptr;       // the approach table (pp_map::atab)
-    double* lanetab = nullptr;    // synth tables: lc_x[NL n] lc_y[NL n] seg_len[NL n] tan_x[NL n] tan_y[NL n]
-    double* arctab = nullptr;     // pp_map::arctab, uploaded on the first follow call (arc_init)
-    std::map<void*, StreamWS> sws;  // per hip_stream
-    void* frame = nullptr;        // single-frame scratch (pp_plan_frame)
-    void* frame_host = nullptr;   // its pinned host staging copy (coherent: k_plan_frame reads and
-                                  // writes it; the frame's done word follows the frame)
-    hipStream_t frame_stream = nullptr;  // pp_plan_frame's stream
-    uint32_t frame_seq = 0;       // the last frame's done word
-    std::mutex frame_mu;          // one pp_plan_frame at a time per device (frame scratch + car table)
-    void* stage = nullptr;        // pp_plan_batch_host staging buffer
-    size_t stage_cap = 0;
-    void* stage_host = nullptr;   // its pinned host mirror (one copy per direction and region)
-    std::mutex stage_mu;          // one pp_plan_batch_host at a time per device
-    pptab::CarTable plan_table;   // pp_plan_frame's persistent car table (the reference's std::map)
-    int timing = 0;               // pp_timing_enable: 0 off, 1 every kernel, 2 K2 only
-    std::vector<hipEvent_t> ev_pool;
-    // groups of 4 kPartMax per pp_eval: before K1, after K1, after K2, after K3/K4 on the launch
-    // stream (the split: those four per part, each part's on its own stream, events 4 h .. 4 h + 3)
-    std::vector<hipEvent_t> ev_rec;
-    // per group: bit 0 K3/K4 launched, bits 1-3 the split's parts (0: none), bit 4 K2's events only,
-    // bit 5 no K1 kernel (the one-launch step)
-    std::vector<int> ev_kind;
-};
-
-}  // namespace
-
-struct pp_map {
-    int n = 0;
-    std::vector<double> geom;     // kMapArrays * n (MapG layout)
-    std::vector<double> ptab;     // (4 + 2 NL) * n: ref xy, normal, lane centres (pp_map_geometry)
-    std::vector<double> lanetab;  // 5 NL * n
-    std::vector<double> arctab;   // reactive traffic's arc prefix (ppfollow::build_arc): cum[NL n] loop[NL]
-    int fastm = 0;                // MapV::fastm: bit 1: every lane segment's rdenom in [2^-500, 2^500]; bit 2: approach_seg's map bounds
-    std::vector<uint2> wgrid;     // closest-waypoint cell table (build_wgrid; empty: none)
-    std::vector<double2> wseg;    // reference segment lengths and reciprocals (build_wseg; empty: none)
-    std::vector<double> atab;     // lane matching's approach table (build_atab; empty: none)
-    WGrid wg;                     // its geometry (cells: the device copy, set per device)
-    DevState dev[kMaxDev];
-    std::mutex mu;
-};
-
-namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int d) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(d); }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// reactive traffic's arc prefix from the host lanetab's seg_len (for a pp_map_create_device map: the
-// mirrored device values), one left-to-right sum per lane
-void fill_arctab(pp_map* M) {
-    M->arctab.assign(ppfollow::arc_doubles(M->n), 0.0);
-    ppfollow::build_arc(M->lanetab.data() + 2 * NL * (size_t)M->n, M->n, M->arctab.data());
-}
-
-// pp_map_geometry's table from the MapG layout: per waypoint ref xy, normal, lane centres
-void fill_ptab(pp_map* M) {
-    const int n = M->n;
-    const double* g = M->geom.data();
-    M->ptab.assign((4 + 2 * NL) * (size_t)n, 0.0);
-    for (int i = 0; i < n; i++) {
-        double* o = &M->ptab[(4 + 2 * NL) * (size_t)i];
-        o[0] = g[i]; o[1] = g[n + i]; o[2] = g[2 * n + i]; o[3] = g[3 * n + i];
-        for (int r = 0; r < NL; r++) { o[4 + 2 * r] = g[(4 + r) * n + i]; o[5 + 2 * r] = g[(4 + NL + r) * n + i]; }
-    }
-    M->fastm = 1;
-    for (size_t i = (size_t)(4 + 3 * NL) * n; i < (size_t)(4 + 4 * NL) * n; i++)
-        if (!(g[i] >= 0x1p-500 && g[i] <= 0x1p500)) M->fastm = 0;
-    // bit 2 (lane matching's approach runs, pp_device.h approach_seg): every lane segment's rdenom
-    // >= 1 m^2 and every lane centre within 4e4 m of the origin
-    bool appr = M->fastm != 0;
-    for (size_t i = (size_t)(4 + 3 * NL) * n; i < (size_t)(4 + 4 * NL) * n; i++) appr = appr && g[i] >= 1.0;
-    for (size_t i = (size_t)4 * n; i < (size_t)(4 + 2 * NL) * n; i++) appr = appr && std::fabs(g[i]) < 4e4;
-    if (appr) M->fastm |= 2;
-}
-
-// The closest-waypoint cell table (pp_device.h WGrid, init_reference_waypoint). Cells of 16 m
-// within 32 m of the waypoint polyline get a list: waypoint w can be the closest one to a point of
-// cell B only if its distance to B, dmin(w, B), is at most U = min over all waypoints of the
-// largest distance from w' to B (the closest waypoint of any point of B is at most U away). B is
-// grown by 0.5 m on each side (the kernel's cell index rounds), and the test carries a relative
-// margin of 1e-6 (the kernel's squared distances round by a few ulps): the list holds every
-// waypoint that can be the scan's answer. Lists of up to 4 (the highway map's cells near the road
-// hold 1-4); a cell with more, or away from the road, has none (0xFFFFFFFF: the kernel scans).
-// Maps of more than 65,535 waypoints, or whose table would take more than 5e7 distance tests to
-// build, get no table.
-constexpr double kWgridMaxCells = 4e6;
-void build_wgrid(pp_map* M) {
-    constexpr double kCell = 16.0, kNear = 32.0, kGrow = 0.5;
-    const int n = M->n;
-    M->wgrid.clear();
-    M->wg = WGrid{};
-    if (n < 1 || n > 65535) return;
-    const double* rx = M->geom.data();
-    const double* ry = rx + n;
-    double x0 = rx[0], x1 = rx[0], y0 = ry[0], y1 = ry[0];
-    for (int i = 0; i < n; i++) {
-        if (!std::isfinite(rx[i]) || !std::isfinite(ry[i])) return;
-        x0 = std::min(x0, rx[i]); x1 = std::max(x1, rx[i]); y0 = std::min(y0, ry[i]); y1 = std::max(y1, ry[i]);
-    }
-    const double gx0 = x0 - 2 * kNear, gy0 = y0 - 2 * kNear;
-    const double wdt = x1 - x0 + 4 * kNear, hgt = y1 - y0 + 4 * kNear;
-    if (!(wdt / kCell < 1e5 && hgt / kCell < 1e5)) return;
-    const int gnx = (int)std::ceil(wdt / kCell), gny = (int)std::ceil(hgt / kCell);
-    // at most 4e6 cells (a 32 km square; 32 MB on the host and the device): a map spread wider
-    // keeps the full scan (two waypoints 1,000 km apart would ask for ~4e9 cells)
-    if ((double)gnx * (double)gny > kWgridMaxCells) return;
-    // cells near the polyline: sample every segment every 2 m, mark cells within kNear
-    std::vector<uint8_t> near((size_t)gnx * gny, 0);
-    const int R = (int)std::ceil(kNear / kCell);
-    for (int i = 0; i < n; i++) {
-        const int j = (i + 1) % n;
-        const double len = std::hypot(rx[j] - rx[i], ry[j] - ry[i]);
-        const int ns = std::max(1, (int)std::ceil(len / 2.0));
-        for (int k = 0; k <= ns; k++) {
-            const double t = (double)k / ns;
-            const double px = rx[i] + (rx[j] - rx[i]) * t, py = ry[i] + (ry[j] - ry[i]) * t;
-            const int ci = (int)((px - gx0) / kCell), cj = (int)((py - gy0) / kCell);
-            for (int dj = -R; dj <= R; dj++)
-                for (int di = -R; di <= R; di++) {
-                    const int a = ci + di, b = cj + dj;
-                    if (a >= 0 && b >= 0 && a < gnx && b < gny) near[(size_t)b * gnx + a] = 1;
-                }
-        }
-    }
-    size_t nnear = 0;
-    for (uint8_t v : near) nnear += v;
-    if ((double)nnear * n > 5e7) return;
-    std::vector<uint2> cells((size_t)gnx * gny, uint2{0xFFFFFFFFu, 0xFFFFFFFFu});
-    std::vector<int> cand;
-    for (int cj = 0; cj < gny; cj++)
-        for (int ci = 0; ci < gnx; ci++) {
-            if (!near[(size_t)cj * gnx + ci]) continue;
-            const double bx0 = gx0 + ci * kCell - kGrow, bx1 = gx0 + (ci + 1) * kCell + kGrow;
-            const double by0 = gy0 + cj * kCell - kGrow, by1 = gy0 + (cj + 1) * kCell + kGrow;
-            double U = INFINITY;
-            for (int i = 0; i < n; i++) {
-                const double fx = std::max(std::fabs(rx[i] - bx0), std::fabs(rx[i] - bx1));
-                const double fy = std::max(std::fabs(ry[i] - by0), std::fabs(ry[i] - by1));
-                U = std::min(U, fx * fx + fy * fy);
-            }
-            const double lim = U * (1 + 1e-6) + 1e-6;
-            cand.clear();
-            for (int i = 0; i < n && cand.size() <= 4; i++) {
-                const double dx = std::max({bx0 - rx[i], rx[i] - bx1, 0.0});
-                const double dy = std::max({by0 - ry[i], ry[i] - by1, 0.0});
-                if (dx * dx + dy * dy <= lim) cand.push_back(i);
-            }
-            if (cand.empty() || cand.size() > 4) continue;
-            while (cand.size() < 4) cand.push_back(cand.back());
-            cells[(size_t)cj * gnx + ci] = uint2{(uint32_t)cand[0] | ((uint32_t)cand[1] << 16),
-                                                 (uint32_t)cand[2] | ((uint32_t)cand[3] << 16)};
-        }
-    M->wgrid.swap(cells);
-    M->wg.gx0 = gx0; M->wg.gy0 = gy0; M->wg.ginv = 1.0 / kCell; M->wg.gnx = gnx; M->wg.gny = gny;
-}
-
-// Map::project_speed's segment length (src/main.cpp:332-339: w = ref_b - ref_{b-1}, |w| =
-// sqrt(wx^2 + wy^2), the same operations as the kernel, unfused, correctly rounded sqrt) and
-// RN(1 / |w|) by IEEE division, per segment b (project_speed then divides by the reciprocal with one
-// Markstein correction: the correctly rounded quotient, ppd::div_by_rcp). Only for maps whose
-// lengths all lie in [2^-500, 2^500] (div_by_rcp's divisor range); else none.
-void build_wseg(pp_map* M) {
-    const int n = M->n;
-    M->wseg.clear();
-    const double* rx = M->geom.data();
-    const double* ry = rx + n;
-    std::vector<double2> t(n);
-    for (int b = 0; b < n; b++) {
-        const int a = (int)(((int64_t)b - 1 + n) % n);
-        const double wx = rx[b] - rx[a], wy = ry[b] - ry[a];
-        const double wvl = std::sqrt(wx * wx + wy * wy);
-        if (!(wvl >= 0x1p-500 && wvl <= 0x1p500)) return;
-        t[b] = double2{wvl, 1.0 / wvl};
-    }
-    M->wseg.swap(t);
-}
-
-// Lane matching's approach table (pp_device.h approach_cert): per lane segment b (waypoint b - 1 to
-// b) and lane l, d = RN(pb - pa) (the walk's own differences), c = pa.d, and the certain test's
-// constants c + rdenom + kAtabMargin (forward) and c - 1 - kAtabMargin (backward), rdenom the map's
-// own table value. Only for maps with fastm bit 2 (the bounds its margin argument needs).
-void build_atab(pp_map* M) {
-    M->atab.clear();
-    if (!(M->fastm & 2)) return;
-    const int n = M->n;
-    const double* g = M->geom.data();
-    const double* lcx = g + 4 * (size_t)n;
-    const double* lcy = g + (4 + NL) * (size_t)n;
-    const double* llen = g + (4 + 2 * NL) * (size_t)n;
-    const double* lden = g + (4 + 3 * NL) * (size_t)n;
-    std::vector<double> t((size_t)kAtabD * n, 0.0);
-    for (int b = 0; b < n; b++) {
-        const int a = b == 0 ? n - 1 : b - 1;
-        double* r = &t[(size_t)kAtabD * b];
-        for (int l = 0; l < NL; l++) {
-            const double pax = lcx[(size_t)l * n + a], pay = lcy[(size_t)l * n + a];
-            const double dx = lcx[(size_t)l * n + b] - pax, dy = lcy[(size_t)l * n + b] - pay;
-            const double c = pax * dx + pay * dy;
-            r[2 * l] = dx;
-            r[2 * l + 1] = dy;
-            r[2 * NL + l] = c + lden[(size_t)l * n + b] + kAtabMargin;
-            r[3 * NL + l] = c - 1.0 - kAtabMargin;
-            r[4 * NL + l] = llen[(size_t)l * n + b];
-        }
-    }
-    M->atab.swap(t);
-}
-
-// The optional per-map tables (cell table, segment reciprocals, approach table) speed K1 up and
-// never change a result: a map whose tables cannot be built (an allocation failure included) runs
-// without them. Nothing here throws across the C-ABI.
-void build_tables(pp_map* M) {
-    try { build_wgrid(M); } catch (...) { M->wgrid.clear(); M->wgrid.shrink_to_fit(); M->wg = WGrid{}; }
-    try { build_wseg(M); } catch (...) { M->wseg.clear(); M->wseg.shrink_to_fit(); }
-    try { build_atab(M); } catch (...) { M->atab.clear(); M->atab.shrink_to_fit(); }
-}
-
-void free_map_tables(DevState& D) {
-    if (D.wgrid) (void)hipFree(D.wgrid);
-    if (D.wseg) (void)hipFree(D.wseg);
-    if (D.atab) (void)hipFree(D.atab);
-    D.wgrid = nullptr; D.wseg = nullptr; D.atab = nullptr;
-}
-
-// the device copies of the cell table, the segment table and the approach table (dev_init,
-// pp_map_create_device)
-int upload_wgrid(pp_map* M, DevState& D) {
-    if (!M->wgrid.empty()) {
-        if (hipMalloc(&D.wgrid, sizeof(uint2) * M->wgrid.size()) != hipSuccess) return PP_ERR_NOMEM;
-        if (hipMemcpy(D.wgrid, M->wgrid.data(), sizeof(uint2) * M->wgrid.size(), hipMemcpyHostToDevice) != hipSuccess)
-            return PP_ERR_HIP;
-    }
-    if (!M->wseg.empty()) {
-        if (hipMalloc(&D.wseg, sizeof(double2) * M->wseg.size()) != hipSuccess) return PP_ERR_NOMEM;
-        if (hipMemcpy(D.wseg, M->wseg.data(), sizeof(double2) * M->wseg.size(), hipMemcpyHostToDevice) != hipSuccess)
-            return PP_ERR_HIP;
-    }
-    if (!M->atab.empty()) {
-        if (hipMalloc(&D.atab, sizeof(double) * M->atab.size()) != hipSuccess) return PP_ERR_NOMEM;
-        if (hipMemcpy(D.atab, M->atab.data(), sizeof(double) * M->atab.size(), hipMemcpyHostToDevice) != hipSuccess)
-            return PP_ERR_HIP;
-    }
-    return PP_OK;
-}
-
-// Map::Init (src/main.cpp:89-131) + derived tables, on the host (done once per map).
-int build_map(pp_map* M, const double* wx, const double* wy, int n) {
-    M->n = n;
-    std::vector<double> nx(n), ny(n), lcx(NL * n), lcy(NL * n);
-    auto W = [n](int i) { return (int)(((int64_t)i + n) % n); };
-    for (int i = 0; i < n; i++) {
-        const int p = W(i - 1);
-        const double dx = wx[i] - wx[p], dy = wy[i] - wy[p];
-        const double len = std::sqrt(dx * dx + dy * dy);
-        if (!(len > 0)) return PP_ERR_ARG;    // duplicate consecutive waypoints: Map::Init divides by 0
-        nx[i] = dy / len;
-        ny[i] = -dx / len;
-    }
-    for (int i = 0; i < n; i++) {
-        const int q = W(i + 1);
-        double ax = (nx[i] + nx[q]) / 2, ay = (ny[i] + ny[q]) / 2;
-        const double a_n = std::atan2(ny[i], nx[i]);
-        const double a_avg = std::atan2(ay, ax);
-        const double cos_alpha = std::cos(a_avg - a_n);
-        ax /= cos_alpha;
-        ay /= cos_alpha;
-        for (int r = 0; r < NL; r++) {
-            const double off = 4.0 * (r + 0.5);
-            lcx[r * n + i] = wx[i] + ax * off;
-            lcy[r * n + i] = wy[i] + ay * off;
-        }
-    }
-    M->geom.assign(kMapArrays * (size_t)n, 0.0);
-    double* g = M->geom.data();
-    for (int i = 0; i < n; i++) {
-        g[i] = wx[i]; g[n + i] = wy[i]; g[2 * n + i] = nx[i]; g[3 * n + i] = ny[i];
-        for (int r = 0; r < NL; r++) {
-            g[(4 + r) * n + i] = lcx[r * n + i];
-            g[(4 + NL + r) * n + i] = lcy[r * n + i];
-            const int p = W(i - 1);
-            const double dx = lcx[r * n + i] - lcx[r * n + p], dy = lcy[r * n + i] - lcy[r * n + p];
-            g[(4 + 2 * NL + r) * n + i] = std::sqrt(dx * dx + dy * dy);    // Map::get_lane_length
-            const double ex = lcx[r * n + p] - lcx[r * n + i], ey = lcy[r * n + p] - lcy[r * n + i];
-            const double den = ex * ex + ey * ey;                           // helpers.h:202 rdenom
-            g[(4 + 3 * NL + r) * n + i] = den;
-            g[(4 + 4 * NL + r) * n + i] = 1.0 / den;
-        }
-    }
-    fill_ptab(M);
-    build_tables(M);
-    M->lanetab.assign(5 * NL * (size_t)n, 0.0);
-    double* t = M->lanetab.data();
-    for (int r = 0; r < NL; r++)
-        for (int i = 0; i < n; i++) {
-            const double len = g[(4 + 2 * NL + r) * n + i];
-            const int p = W(i - 1);
-            t[0 * NL * n + r * n + i] = lcx[r * n + i];
-            t[1 * NL * n + r * n + i] = lcy[r * n + i];
-            t[2 * NL * n + r * n + i] = len;
-            t[3 * NL * n + r * n + i] = (lcx[r * n + i] - lcx[r * n + p]) / len;
-            t[4 * NL * n + r * n + i] = (lcy[r * n + i] - lcy[r * n + p]) / len;
-        }
-    fill_arctab(M);
-    return PP_OK;
-}
-
-ppsynth::OutBatch out_batch(const pp_scene_batch* b) {
-    ppsynth::OutBatch o;
-    o.S = b->n_scenes;
-    o.ego_x = (double*)b->ego_x; o.ego_y = (double*)b->ego_y;
-    o.ego_yaw_deg = (double*)b->ego_yaw_deg; o.ego_speed_mph = (double*)b->ego_speed_mph;
-    o.prev_x = (double*)b->prev_x; o.prev_y = (double*)b->prev_y;
-    o.n_prev = (int32_t*)b->n_prev; o.prev_target_lane = (int32_t*)b->prev_target_lane;
-    o.n_cars = (int32_t*)b->n_cars; o.car_id = (int32_t*)b->car_id;
-    o.car_x = (double*)b->car_x; o.car_y = (double*)b->car_y;
-    o.car_vx = (double*)b->car_vx; o.car_vy = (double*)b->car_vy;
-    return o;
-}
-
-bool traffic_ok(const pp_traffic* t, const pp_scene_batch* b) {
-    return t && b && t->n_cars >= 0 && t->n_cars <= PP_MAX_CARS && t->lane && t->seg && t->t &&
-           t->offset && t->speed;
-}
-
-bool judge_ok(const pp_judge_cfg* c, const pp_judge* j) {
-    return c && j && ppjudge::cfg_ok(*c) && j->steps && j->flags && j->count && j->first_step &&
-           j->first_car && j->seg_hint && j->off_run && j->head_x && j->head_y && j->ring_vx && j->ring_vy &&
-           j->dist && j->clean_dist && j->min_sep && j->max_speed_mph && j->max_acc && j->max_jerk;
-}
-
-// what the judge reads of a frame: the ego pose, the traffic, the plan
-bool judge_frame_ok(const pp_scene_batch* tel, const pp_traffic* traffic, const pp_result* plan, int32_t consume) {
-    return tel && plan && tel->n_scenes >= 0 && tel->ego_x && tel->ego_y && tel->ego_yaw_deg &&
-           traffic_ok(traffic, tel) && plan->n_out && plan->next_x && plan->next_y && consume >= 1;
-}
-
-bool follow_ok(const pp_follow_cfg* c, const pp_follow* f) {
-    return c && f && ppfollow::cfg_ok(*c) && f->started && f->ego_seg && f->desired && f->next_speed &&
-           f->leader && f->gap;
-}
-
-// what the follow update reads of a frame: the ego's position and speed, the traffic
-bool follow_frame_ok(const pp_scene_batch* tel, const pp_traffic* traffic, int32_t consume) {
-    return tel && tel->n_scenes >= 0 && tel->ego_x && tel->ego_y && tel->ego_speed_mph &&
-           traffic_ok(traffic, tel) && consume >= 1;
-}
-
-ppsynth::TrafficV traffic_view(const pp_traffic* t, int64_t S) {
-    ppsynth::TrafficV v;
-    v.S = S; v.n = t->n_cars; v.lane = t->lane; v.seg = t->seg; v.t = t->t; v.off = t->offset; v.v = t->speed;
-    return v;
-}
-
-ppsynth::LaneTables lane_tables(const double* t, int n) {
-    ppsynth::LaneTables T;
-    T.n = n; T.lc_x = t; T.lc_y = t + NL * n; T.seg_len = t + 2 * NL * n; T.tan_x = t + 3 * NL * n;
-    T.tan_y = t + 4 * NL * n;
-    return T;
-}
-
-int dev_init(pp_map* M, int device) {
-    DevState& D = M->dev[device];
-    if (D.init) return PP_OK;
-    if (hipMalloc(&D.map, sizeof(double) * M->geom.size()) != hipSuccess) return PP_ERR_NOMEM;
-    if (hipMalloc(&D.lanetab, sizeof(double) * M->lanetab.size()) != hipSuccess) return PP_ERR_NOMEM;
-    if (hipMemcpy(D.map, M->geom.data(), sizeof(double) * M->geom.size(), hipMemcpyHostToDevice) != hipSuccess) return PP_ERR_HIP;
-    if (hipMemcpy(D.lanetab, M->lanetab.data(), sizeof(double) * M->lanetab.size(), hipMemcpyHostToDevice) != hipSuccess) return PP_ERR_HIP;
-    const int rc = upload_wgrid(M, D);
-    if (rc != PP_OK) return rc;
-    D.init = true;
-    return PP_OK;
-}
-
-// the device copy of the arc prefix, made on the first follow call on this device (after dev_init,
-// under M->mu)
-int arc_init(pp_map* M, int device) {
-    DevState& D = M->dev[device];
-    if (D.arctab) return PP_OK;
-    if (hipMalloc(&D.arctab, sizeof(double) * M->arctab.size()) != hipSuccess) return PP_ERR_NOMEM;
-    if (hipMemcpy(D.arctab, M->arctab.data(), sizeof(double) * M->arctab.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(D.arctab);
-        D.arctab = nullptr;
-        return PP_ERR_HIP;
-    }
-    return PP_OK;
-}
-
-size_t prep_bytes(int64_t S) { return ((size_t)S * (kPrepD * 8 + kPrepI * 4) + 255) / 256 * 256; }
-// reference-mode winner record (k_cand -> k_emit): 3 x PP_MAX_POINTS x S doubles + 2 x S u64
-size_t rec_bytes(int64_t S) { return (size_t)S * (3 * PP_MAX_POINTS + 2) * 8 + 256; }
-static_assert(kWinRec <= 3 * PP_MAX_POINTS + 2, "the stored winner slots share the record's memory");
-double* rec_buf(void* rec) { return (double*)rec; }
-uint64_t* adj_buf(void* rec, int64_t cap) { return (uint64_t*)((double*)rec + 3 * PP_MAX_POINTS * cap); }
-
-
-PrepV prep_bind(void* base, int64_t S) {
-    PrepV p;
-    double* d = (double*)base;
-    double** dd[] = {&p.pos_x, &p.pos_y, &p.angle, &p.ca_m, &p.sa_m, &p.ca_p, &p.sa_p,
-                     &p.ego_speed, &p.ego_d, &p.ego_vd, &p.in_ts, &p.in_tt};
-    int k = 0;
-    for (double** q : dd) *q = d + (int64_t)(k++) * S;
-    p.ratio = d + (int64_t)(k) * S; k += NL;
-    p.l_ts = d + (int64_t)(k) * S; k += NL;
-    p.l_tt = d + (int64_t)(k) * S; k += NL;
-    p.score = d + (int64_t)(k) * S; k += NL;
-    // k == kPrepD
-    int32_t* ip = (int32_t*)(d + (int64_t)kPrepD * S);
-    int32_t** ii[] = {&p.K, &p.ref_wp, &p.T, &p.ego_lane, &p.open_mask, &p.lim_mask, &p.status};
-    int m = 0;
-    for (int32_t** q : ii) *q = ip + (int64_t)(m++) * S;
-    return p;
-}
-
-// pp_debug_set's switches (include/pp.h PP_DBG_*): launch-shape overrides for tests and A/B
-// measurements. Every one defaults to 0 = the product's own choice; nothing reads the environment.
-std::atomic<int> g_dbg[PP_DBG_KEYS];
-int dbg(int key) { return g_dbg[key].load(std::memory_order_relaxed); }
-
-// K4 inside k_cand: the winners' sin/cos tables (2 N doubles each) fit the block's spline slots
-bool emit_in_ok(int N) { return 2 * N <= 5 * NL * kKP; }
-// small reference-mode batches (<= kFusedSmall scenes): K2 + K4 in one launch (k_cand_small) or the
-// whole step in one launch (k_step_small); PP_DBG_SHAPE forces one of the three shapes
-constexpr int64_t kFusedSmall = 16384;
-bool fused_small(int64_t S) {
-    const int f = dbg(PP_DBG_SHAPE);
-    return f ? f != PP_SHAPE_SPLIT : S <= kFusedSmall;
-}
-bool step_fused_on() { return dbg(PP_DBG_SHAPE) != PP_SHAPE_CAND_SMALL; }
-// Two-stream split (reference mode, no paths): batches of about one 8-GPU shard of BASELINE config 5
-// (262,144 scenes) run as two halves, each K1 -> K2 -> K4 on its own stream, so one half's kernels
-// fill the other's start-up and tail (a batch this size is ~15 rounds of k_cand blocks and one of
-// k_prep waves). Up to config 5's N = 2 shard (1,048,576 scenes: 4.96-4.99 ms against
-// 5.09-5.15 unsplit, same boxes); the full 2,097,152-scene batch stays one stream (9.87-9.91 against
-// 9.93-9.96 ms split, within the boxes' spread, and its K2 span is 0.3 ms longer than the unsplit
-// K2). PP_DBG_SPLIT 1 forces it for every batch the split can take (reference mode without paths
-// or draws, one K1 lane per scene: more than 65,536 scenes, prep_group), 2 turns it off; the parts
-// of the last call are read back with PP_DBG_LAST_PARTS.
-constexpr int64_t kSplitMin = 131072, kSplitMaxScenes = 1572864;
-#ifndef PP_SPLIT_BIG
-#define PP_SPLIT_BIG 0        // 1: batches beyond kSplitMaxScenes run as chunks (A/B builds)
-#endif
-constexpr int64_t kChunkScenes = 1048576;
-bool split_on(int64_t S) {
-    const int f = dbg(PP_DBG_SPLIT);
-    if (f == 2) return false;
-    // forced: any batch of at least 2,048 scenes (its parts then never come out empty)
-    if (f == 1) return S >= 2048;
-    return S >= kSplitMin && (S <= kSplitMaxScenes || PP_SPLIT_BIG);
-}
-// parts of a split batch: 2 up to 393,216 scenes (BASELINE config 5's N = 8 shard, 262,144: 1.32 ms
-// against 1.35 / 1.37 ms with 3 / 4 parts), 3 beyond (its N = 4 shard, 524,288: 2.52 ms against
-// 2.59-2.62 with 2 parts and 2.60 unsplit; profiles/r04_ablations.txt)
-int split_parts(int64_t S) {
-    if (PP_SPLIT_PARTS >= 2 && PP_SPLIT_PARTS <= kSplitMax) return PP_SPLIT_PARTS;
-    return S > 393216 ? 3 : 2;
-}
-// chunks of a split batch: a batch beyond kSplitMaxScenes, when split (PP_DBG_SPLIT 1, or
-// PP_SPLIT_BIG builds), runs as ceil(S / 1,048,576) sequential chunks of split_parts parts each
-// (chunk c + 1 starts when every part of chunk c has ended). Round 6 measured it for BASELINE
-// config 5 (2,097,152 scenes; tools/chunk_probe.py, profiles/r06_chunk_probe*.txt): two separate
-// pp_eval calls of 1,048,576 scenes (their own arrays) ran 9.78-9.87 ms against 9.79-9.99 for
-// one call on one stream, but the same chunks inside one call (the batch's own arrays) ran
-// 9.98-10.01 on the box where the separate calls took 9.85, and 6 parts pipelined over the 3
-// streams without the join 10.00-10.07: the full batch stays on one stream.
-int split_chunks(int64_t S) {
-    if (S <= kSplitMaxScenes) return 1;
-    const int64_t c = (S + kChunkScenes - 1) / kChunkScenes;
-    return (int)std::min<int64_t>(c, kPartMax / kSplitMax);
-}
-// K1 (one lane per evaluation): 3 waves per SIMD, or 4 where the batch's waves fill whole rounds of
-// 4 better. Round 5 (the approach table in the 3-wave build's LDS): a round of 3 waves per SIMD
-// takes ~0.150 ms (config 5: 1.65 ms for 32,768 waves = 11 rounds), one of 4 ~0.357 ms (spills,
-// the table in global memory); 262,144 scenes = 4,096 waves: 0.297 ms at 3, 0.357 at 4
-// (profiles/r05_ablations.txt), so the 4-wave build no longer wins at any size (round 4: 0.188 /
-// 0.286 ms per round, 4 waves at 262,144). PP_DBG_PREP_WAVES forces 3 or 4.
-int cu_count(int device) {
-    static int cus[kMaxDev] = {};
-    if (device < 0 || device >= kMaxDev) return 256;
-    if (cus[device] == 0) {
-        int c = 0;
-        if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || c <= 0) c = 256;
-        cus[device] = c;
-    }
-    return cus[device];
-}
-// the one-launch step with phase A beside K1 (wave_step_body) where its blocks fit one per CU:
-// 8-scene blocks of 256 threads (the frame, batches up to 2,048 scenes: 0.128 -> 0.116 ms at 2,048),
-// else 16-scene blocks of 512 threads; beyond, 16-scene blocks of 256 threads, K1 then phase A
-// (2 blocks of 8 per CU measured slower: config 2 0.132 against 0.128 ms, profiles/r04_ablations.txt)
-int step_waves_on(int64_t S, int spb, int device) {
-    if (!kStepWaves) return 0;
-    if ((S + kStepWaveSpb - 1) / kStepWaveSpb <= cu_count(device)) return 1;
-    if (spb >= 16 && (S + 15) / 16 <= cu_count(device)) return 2;
-    return 0;
-}
-bool prep_w4(int64_t Sv, int device) {
-    const int f = dbg(PP_DBG_PREP_WAVES);
-    if (f == 3 || f == 4) return f == 4;
-    const int64_t waves = (Sv + 63) / 64, simds = 4LL * cu_count(device);
-    const int64_t r3 = (waves + 3 * simds - 1) / (3 * simds), r4 = (waves + 4 * simds - 1) / (4 * simds);
-    return 357 * r4 < 150 * r3;
-}
-// k_emit: batches up to this many scenes take the small-batch instantiation
-constexpr int64_t kEmitSmall = 65536;
-// K1 lanes per evaluation: the largest power of two <= 16 that keeps Sv * G within ~2 waves per
-// SIMD of the chip (256 CUs x 4 SIMDs x 64 lanes x 2); 1 for large batches. PP_DBG_PREP_GROUP
-// forces a value.
-bool prep_group_ok(int G) { return G == 0 || G == 1 || G == 2 || G == 4 || G == 8 || G == 16; }
-int prep_group(int64_t Sv) {
-    const int forced = dbg(PP_DBG_PREP_GROUP);
-    if (forced > 0) return forced;
-    const int64_t target = 256LL * 4 * 64 * 2;
-    int G = 1;
-    while (G < 16 && Sv * G * 2 <= target) G *= 2;
-    return G;
-}
-
-// Scenes per k_cand group (C <= 256): at most 256 / C (one 256-lane block) and 64 / NL (spline
-// slots: phase A's serial steps run on one wave), chosen so the block's waves carry the fewest
-// idle lanes through phase B (largest such count on ties): C = 15 -> 17 scenes (255 of 256
-// lanes), C = 24 (config 3) -> 8 scenes in exactly 3 waves instead of 10 in 4 waves with 16 idle
-// lanes.
-int cands_per_block(int C) {
-    int hi = 256 / C;
-    if (hi > 64 / NL) hi = 64 / NL;
-    if (hi < 1) return 1;
-    int best = hi;
-    double bu = 0;
-    for (int spb = hi; spb >= 1; spb--) {
-        const int t = spb * C;
-        const double u = (double)t / (double)(((t + 63) / 64) * 64);
-        if (u > bu + 1e-9) { bu = u; best = spb; }
-    }
-    return best;
-}
-
-// callers hold M->mu; `st` is the stream the workspace belongs to
-int ensure_ws(StreamWS& W, hipStream_t st, int64_t Sv) {
-    if (W.ws_cap >= Sv) return PP_OK;
-    if (W.ws) { (void)hipStreamSynchronize(st); (void)hipFree(W.ws); W.ws = nullptr; W.ws_cap = 0; }
-    if (hipMalloc(&W.ws, prep_bytes(Sv)) != hipSuccess) return PP_ERR_NOMEM;
-    W.ws_cap = Sv;
-    return PP_OK;
-}
-
-// k_sort_cars' output for S scenes of `rows` rows each (SortedCars over one allocation)
-size_t srt_bytes(int64_t S, int rows) { return (size_t)S * ((size_t)rows * (4 * sizeof(double) + sizeof(int)) + 8) + 256; }
-int ensure_srt(StreamWS& W, hipStream_t st, int64_t S, int rows, SortedCars& sc) {
-    const size_t need = srt_bytes(S, rows);
-    if (W.srt_cap < need) {
-        if (W.srt) { (void)hipStreamSynchronize(st); (void)hipFree(W.srt); W.srt = nullptr; W.srt_cap = 0; }
-        if (hipMalloc(&W.srt, need) != hipSuccess) return PP_ERR_NOMEM;
-        W.srt_cap = need;
-    }
-    double* b = (double*)W.srt;
-    const int64_t n = (int64_t)rows * S;
-    sc.x = b; sc.y = b + n; sc.vx = b + 2 * n; sc.vy = b + 3 * n;
-    sc.id = (int*)(b + 4 * n);
-    sc.order = (uint64_t*)(((uintptr_t)(sc.id + n) + 7) & ~(uintptr_t)7);
-    sc.rows = rows;
-    return PP_OK;
-}
-
-int ensure_rec(StreamWS& W, hipStream_t st, int64_t S) {
-    const int64_t cap = (S + 63) & ~(int64_t)63;   // whole 64-scene blocks
-    if (W.rec_cap >= cap) return PP_OK;
-    if (W.rec) { (void)hipStreamSynchronize(st); (void)hipFree(W.rec); W.rec = nullptr; W.rec_cap = 0; }
-    if (hipMalloc(&W.rec, rec_bytes(cap)) != hipSuccess) return PP_ERR_NOMEM;
-    W.rec_cap = cap;
-    return PP_OK;
-}
-
-// The slow-group bitmap (words), then the flagged-group count and list (ngroups entries), in one
-// allocation: [cap words][count][list: 32 cap entries]
-int ensure_gbits(StreamWS& W, hipStream_t st, int64_t ngroups) {
-    const int64_t words = (ngroups + 31) / 32;
-    if (W.gbits_cap >= words) return PP_OK;
-    if (W.gbits) { (void)hipStreamSynchronize(st); (void)hipFree(W.gbits); W.gbits = nullptr; W.gbits_cap = 0; }
-    const int64_t cap = std::max<int64_t>(words, 1024);
-    // [bits: cap words][flagged-group count][the split's second-half count][list: 32 cap entries]
-    const size_t bytes = sizeof(uint32_t) * (size_t)(cap + kPartMax + 32 * cap);
-    if (hipMalloc(&W.gbits, bytes) != hipSuccess) return PP_ERR_NOMEM;
-    if (hipMemsetAsync(W.gbits, 0, bytes, st) != hipSuccess) return PP_ERR_HIP;
-    W.gbits_cap = cap;
-    return PP_OK;
-}
-
-void free_ws(StreamWS& W) {
-    for (int k = 0; k < kSplitMax - 1; k++) {
-        if (W.st2[k]) (void)hipStreamDestroy(W.st2[k]);
-        if (W.join[k]) (void)hipEventDestroy(W.join[k]);
-    }
-    if (W.fork) (void)hipEventDestroy(W.fork);
-    if (W.ws) (void)hipFree(W.ws);
-    if (W.rec) (void)hipFree(W.rec);
-    if (W.gbits) (void)hipFree(W.gbits);
-    if (W.srt) (void)hipFree(W.srt);
-    W = StreamWS();
-}
-
-// k_cand's launch geometry for C candidates per scene (BPS == 1: SPB scenes per group; else one
-// scene over BPS groups of 256 candidates)
-struct CandGeom { int spb, bps, threads; size_t lds; int64_t groups; };
-// k_cand's LDS for SPB scenes per group: slots (5 x kKP doubles + 4 ints each), sFlags/sSlow,
-// then (8-aligned) sAdj and sNg
-size_t cand_geom_lds(int spb) {
-    const int nslot = NL * spb;
-    size_t lds = sizeof(double) * 5 * kKP * (size_t)nslot + sizeof(int) * 4 * nslot + sizeof(uint32_t) * 2 * spb;
-    return ((lds + 7) & ~(size_t)7) + sizeof(uint64_t) * 2 * spb + sizeof(int) * spb;
-}
-// the flat geometry for the all-paths mode (kMode 2): 256-lane groups over the batch's candidates,
-// scenes straddling two groups (their spline slots built in both, status flags merged with
-// atomics): four full waves per block where whole scenes would leave a wave slot of the CU idle
-// (C = 24: 8 scenes in 3 waves, 5 blocks = 15 of 16 waves per CU). Up to (C + 254) / C + 1 scenes
-// per group; C >= 13 keeps those slots within the first wave (NL SPB <= 64 for phase A's serial steps)
-#ifndef PP_CAND_FLAT
-#define PP_CAND_FLAT 1
-#endif
-bool cand_flat_ok(int C) { return PP_CAND_FLAT && C >= 13 && C <= 128 && 256 % C != 0; }
-CandGeom cand_geom(int C, int64_t S, bool flat = false) {
-    CandGeom g;
-    if (flat) {
-        g.spb = (C + 254) / C + 1;
-        g.bps = -1;
-        g.threads = 256;
-        g.lds = cand_geom_lds(g.spb);
-        g.groups = (S * C + 255) / 256;
-        return g;
-    }
-    g.spb = C <= 256 ? cands_per_block(C) : 1;
-    g.bps = C <= 256 ? 1 : (C + 255) / 256;
-    g.threads = C <= 256 ? ((g.spb * C + 63) / 64) * 64 : 256;
-    g.lds = cand_geom_lds(g.spb);
-    g.groups = g.bps == 1 ? (S + g.spb - 1) / g.spb : S * g.bps;
-    return g;
-}
-
-int n_draws(const pp_params* p) { return p->n_draws > 1 ? p->n_draws : 1; }
-
-// k_prep<true, false>'s LDS with the approach table after the map (MapG::atab_lds)
-size_t prep_lds_atab(int n) {
-    return sizeof(double) * (((kMapArrays * (size_t)n + 1) & ~(size_t)1) + kAtabD * (size_t)n);
-}
-
-
-bool params_ok(const pp_params* p) {
-    return p && p->n_points > PP_PREV_KEEP && p->n_points <= PP_MAX_POINTS && p->n_speeds >= 1 &&
-           p->n_speeds <= PP_MAX_SPEEDS && NL * p->n_speeds <= 256 &&
-           (p->cost_mode == PP_COST_REFERENCE || p->cost_mode == PP_COST_COMFORT) &&
-           p->n_draws >= 0 && p->n_draws <= PP_MAX_DRAWS && p->noise_first_scene >= 0 &&
-           !(p->n_draws > 1 && p->emit_paths);
-}
-
-}  // namespace
-
-extern "C" {
-
-void pp_params_default(pp_params* p) {
-    if (!p) return;
-    memset(p, 0, sizeof(*p));
-    p->n_points = 50;
-    p->n_speeds = 5;
-    p->cost_mode = PP_COST_REFERENCE;
-    p->emit_paths = 0;
-    const double offs[4] = {-4.0, -2.0, 0.0, 2.0};      // SURVEY.md §8(d) speed grid
-    for (int i = 0; i < 4; i++) p->speed_offsets[i] = offs[i];
-    p->relaxed_acc = 5;                  // src/main.cpp:39-49
-    p->min_relaxed_acc_while_braking = 4;
-    p->maximum_acc = 8;
-    p->max_speed = 22.2;
-    p->car_length = 4.5;
-    p->safety_distance = 2;
-    p->keep_distance = 10;
-    p->keep_distance_leeway = 0.5;
-    p->n_draws = 0;
-    p->noise_seed = 0x5EED0002ull;
-    p->noise_first_scene = 0;
-    p->noise_pos_sigma = 0.5;            // SURVEY.md §8(d) Monte-Carlo
-    p->noise_vel_sigma = 0.5;
-}
-
-int32_t pp_num_candidates(const pp_params* p) { return p ? n_draws(p) * NL * p->n_speeds : 0; }
-
-int32_t pp_num_lanes(void) { return NL; }
-
-int32_t pp_max_cars(void) { return PP_MAX_CARS; }
-
-double pp_mc_gauss(uint64_t seed, int64_t scene, int32_t draw, int32_t car, int32_t q) {
-    return ppsynth::mc_gauss(seed, (uint64_t)scene, draw, car, q);
-}
-
-#ifdef PP_CHECK
-int32_t pp_check_read(unsigned long long* out, int32_t reset) {  // checking builds only: g_chk[8]
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_chk), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[8] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_chk), z, sizeof z) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
-#ifdef PP_TRACE
-int32_t pp_trace_read(unsigned long long* out, int64_t words) {   // diagnostic builds only: g_trace
-    if (words > 8LL * kTraceMax) words = 8LL * kTraceMax;
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trace), sizeof(unsigned long long) * words) != hipSuccess) return -1;
-    return 0;
-}
-#endif
-#if defined(PP_DIAG) || defined(PP_LIMCENSUS)
-int32_t pp_diag_read(unsigned long long* out, int32_t reset) {   // diagnostic builds only (96 words)
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_diag), sizeof(unsigned long long) * kDiagWords) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[kDiagWords] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_diag), z, sizeof z) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
-int32_t pp_libm_eval(int32_t kind, const double* a, const double* b, double* out, int64_t n,
-                     int32_t device, void* hip_stream) {
-    if (kind < 0 || kind > 2 || n < 0 || (n > 0 && (!a || !out || (kind == 2 && !b))) || device < -1 ||
-        device >= kMaxDev)
-        return PP_ERR_ARG;
-    if (n == 0) return PP_OK;
-    if (device < 0) {
-        for (int64_t i = 0; i < n; i++) {
-            double r = __builtin_nan("");
-            if (kind == 0) ppg::sin(a[i], r);
-            else if (kind == 1) ppg::cos(a[i], r);
-            else r = ppg::atan2(a[i], b[i]);
-            out[i] = r;
-        }
-        return PP_OK;
-    }
-    DeviceGuard g(device);
-    const int64_t blocks = (n + 255) / 256;
-    if (blocks > 0x7fffffff) return PP_ERR_ARG;
-    hipLaunchKernelGGL(k_libm, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, kind, a, b, out, n);
-    return hipGetLastError() == hipSuccess ? PP_OK : PP_ERR_HIP;
-}
-
-const char* pp_version(void) { return "pp-mi355x 0.1 (gfx950, fp64, lane-per-candidate)"; }
-
-int32_t pp_map_create(const double* wx, const double* wy, int32_t n, pp_map** out) {
-    if (!wx || !wy || !out || n < 3 || n > kMaxWaypoints) return PP_ERR_ARG;
-    pp_map* M = new (std::nothrow) pp_map();
-    if (!M) return PP_ERR_NOMEM;
-    int rc;
-    try { rc = build_map(M, wx, wy, n); } catch (...) { rc = PP_ERR_NOMEM; }   // (host allocations)
-    if (rc != PP_OK) { delete M; return rc; }
-    *out = M;
-    return PP_OK;
-}
-
-// Map::Init on the device from device waypoint arrays; the derived tables are mirrored to the host
-// (for pp_map_geometry, the host generator and other devices).
-static int32_t map_create_device(const double* d_wx, const double* d_wy, int32_t n, int32_t device,
-                                 void* hip_stream, pp_map** out);
-int32_t pp_map_create_device(const double* d_wx, const double* d_wy, int32_t n, int32_t device, void* hip_stream,
-                             pp_map** out) {
-    try { return map_create_device(d_wx, d_wy, n, device, hip_stream, out); } catch (...) { return PP_ERR_NOMEM; }
-}
-static int32_t map_create_device(const double* d_wx, const double* d_wy, int32_t n, int32_t device,
-                                 void* hip_stream, pp_map** out) {
-    if (!d_wx || !d_wy || !out || n < 3 || n > kMaxWaypoints || device < 0 || device >= kMaxDev) return PP_ERR_ARG;
-    pp_map* M = new (std::nothrow) pp_map();
-    if (!M) return PP_ERR_NOMEM;
-    M->n = n;
-    DeviceGuard g(device);
-    DevState& D = M->dev[device];
-    hipStream_t st = (hipStream_t)hip_stream;
-    int* bad = nullptr;
-    if (hipMalloc(&D.map, sizeof(double) * kMapArrays * (size_t)n) != hipSuccess ||
-        hipMalloc(&D.lanetab, sizeof(double) * 5 * NL * (size_t)n) != hipSuccess || hipMalloc(&bad, sizeof(int)) != hipSuccess) {
-        if (D.map) (void)hipFree(D.map);
-        if (D.lanetab) (void)hipFree(D.lanetab);
-        delete M;
-        return PP_ERR_NOMEM;
-    }
-    int rc = PP_OK;
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    if (hipMemsetAsync(bad, 0, sizeof(int), st) != hipSuccess) rc = PP_ERR_HIP;
-    hipLaunchKernelGGL(k_map_normals, dim3(blocks), dim3(256), 0, st, d_wx, d_wy, n, D.map, bad);
-    hipLaunchKernelGGL(k_map_lanes, dim3(blocks), dim3(256), 0, st, n, D.map);
-    hipLaunchKernelGGL(k_map_lengths, dim3(blocks), dim3(256), 0, st, n, D.map, D.lanetab);
-    if (hipGetLastError() != hipSuccess) rc = PP_ERR_HIP;
-    int hbad = 0;
-    M->geom.assign(kMapArrays * (size_t)n, 0.0);
-    M->lanetab.assign(5 * NL * (size_t)n, 0.0);
-    if (rc == PP_OK && (hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipMemcpyAsync(M->geom.data(), D.map, sizeof(double) * kMapArrays * (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipMemcpyAsync(M->lanetab.data(), D.lanetab, sizeof(double) * 5 * NL * (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipStreamSynchronize(st) != hipSuccess))
-        rc = PP_ERR_HIP;
-    (void)hipFree(bad);
-    if (rc == PP_OK && hbad) rc = PP_ERR_ARG;          // Map::Init divides by a zero segment length
-    if (rc != PP_OK) {
-        (void)hipFree(D.map); (void)hipFree(D.lanetab);
-        D.map = D.lanetab = nullptr;
-        delete M;
-        return rc;
-    }
-    fill_ptab(M);
-    build_tables(M);
-    fill_arctab(M);
-    if (upload_wgrid(M, D) != PP_OK) {
-        free_map_tables(D);
-        (void)hipFree(D.map); (void)hipFree(D.lanetab);
-        delete M;
-        return PP_ERR_NOMEM;
-    }
-    D.init = true;
-    *out = M;
-    return PP_OK;
-}
-
-int32_t pp_map_destroy(pp_map* M) {
-    if (!M) return PP_ERR_ARG;
-    for (int d = 0; d < kMaxDev; d++) {
-        DevState& D = M->dev[d];
-        if (!D.init) continue;
-        DeviceGuard g(d);
-        (void)hipDeviceSynchronize();
-        (void)hipFree(D.map); (void)hipFree(D.lanetab);
-        if (D.arctab) (void)hipFree(D.arctab);
-        free_map_tables(D);
-        for (auto& kv : D.sws) free_ws(kv.second);
-        D.sws.clear();
-        if (D.frame) (void)hipFree(D.frame);
-        if (D.frame_host) (void)hipHostFree(D.frame_host);
-        if (D.frame_stream) (void)hipStreamDestroy(D.frame_stream);
-        if (D.stage) (void)hipFree(D.stage);
-        if (D.stage_host) (void)hipHostFree(D.stage_host);
-        for (hipEvent_t e : D.ev_pool) (void)hipEventDestroy(e);
-        for (hipEvent_t e : D.ev_rec) (void)hipEventDestroy(e);
-    }
-    delete M;
-    return PP_OK;
-}
-
-int32_t pp_map_geometry(const pp_map* M, double* out, int32_t n) {
-    if (!M || !out || n != M->n) return PP_ERR_ARG;
-    memcpy(out, M->ptab.data(), sizeof(double) * (4 + 2 * NL) * (size_t)n);
-    return PP_OK;
-}
-
-int32_t pp_reserve(pp_map* M, int32_t device, int64_t max_scenes) {
-    if (!M || device < 0 || device >= kMaxDev || max_scenes < 0) return PP_ERR_ARG;
-    std::lock_guard<std::mutex> lk(M->mu);
-    DeviceGuard g(device);
-    int rc = dev_init(M, device);
-    if (rc) return rc;
-    StreamWS& W = M->dev[device].sws[nullptr];       // the null stream's workspace
-    rc = ensure_ws(W, nullptr, max_scenes);
-    if (rc) return rc;
-    return ensure_rec(W, nullptr, max_scenes);
-}
-
-}  // extern "C"
-namespace {
-// pp_eval; fio (pp_plan_frame): the single-launch frame kernel with host-memory staging, where the
-// call takes the fused one-launch shape (PP_ERR_STATE otherwise: the caller stages by copies)
-int32_t eval_impl(pp_map* M, const pp_scene_batch* in, const pp_params* prm, pp_result* out,
-                  int32_t device, void* hip_stream, const FrameIO* fio) {
-    if (!M || !in || !out || !params_ok(prm) || device < 0 || device >= kMaxDev) return PP_ERR_ARG;
-    if (in->n_scenes < 0 || in->car_stride < 0 || in->car_stride > PP_MAX_CARS) return PP_ERR_ARG;
-    if (in->n_scenes == 0) return PP_OK;
-    if (!in->ego_x || !in->ego_y || !in->ego_yaw_deg || !in->ego_speed_mph || !in->prev_x ||
-        !in->prev_y || !in->n_prev || !in->prev_target_lane || !in->n_cars ||
-        (in->car_stride > 0 && (!in->car_id || !in->car_x || !in->car_y || !in->car_vx || !in->car_vy)))
-        return PP_ERR_ARG;
-    if (!out->winner || !out->n_out || !out->next_x || !out->next_y || !out->cost || !out->status)
-        return PP_ERR_ARG;
-    if (prm->emit_paths && !out->paths) return PP_ERR_ARG;
-    if (in->tab_valid && (!in->tab_lane || !in->tab_s || !in->tab_d || !in->tab_vs || !in->tab_vd ||
-                          !in->tab_vx || !in->tab_vy || prm->n_draws > 1 || in->tab_slots < 0 ||
-                          in->tab_slots > PP_MAX_CARS))
-        return PP_ERR_ARG;
-    DeviceGuard g(device);
-    hipStream_t st = (hipStream_t)hip_stream;
-    const int64_t S = in->n_scenes;
-    const int Dn = n_draws(prm);
-    const int64_t Sv = S * Dn;                    // evaluations (scene x draw)
-    // reference decision without draws: the winner is known before the loop (k_cand records it,
-    // k_emit writes it); otherwise the decision is a cost argmin (k_winner)
-    const bool ref_direct = prm->cost_mode == PP_COST_REFERENCE && Dn == 1;
-    const int Cn_ = Dn * NL * prm->n_speeds;
-    const CandGeom cg = cand_geom(Cn_, S, prm->emit_paths && Dn == 1 && cand_flat_ok(Cn_));
-    if (cg.groups > 0x7fffffff) return PP_ERR_ARG;
-    // small batches in reference mode without paths: K2 and K4 in one launch (k_cand_small, K4 in
-    // the block: emit_in), unless the horizon's sin/cos table (2 N doubles per winner) exceeds the
-    // block's spline slots. Large batches keep K4 in its own kernel: in the block, the serial
-    // replay holds the block's LDS and costs k_cand more than k_emit takes.
-    const bool fused = ref_direct && !prm->emit_paths && cg.bps == 1 && emit_in_ok(prm->n_points) &&
-                       fused_small(S);
-    const bool emit_in = fused;
-    // small reference-mode batches with the map in LDS: the whole step in one launch (k_step_small)
-    // (kStepWaves: blocks of up to kStepWaveSpb scenes in 256 threads, K1 and phase A side by side,
-    // plus the per-scene geometry records; otherwise up to 16 scenes, K1 then phase A)
-    // step_waves: 1 blocks of 8 scenes in 256 threads, 2 blocks of 16 scenes in 512 threads, 0 the
-    // 16-scene blocks without the split
-    int step_waves = step_waves_on(S, cg.spb, device);
-    const size_t map_lds = sizeof(double) * (size_t)((kMapArrays * M->n + 1) & ~1);
-    auto step_lds = [&](int wv, int spb) {
-        return map_lds + (wv != 0 ? sizeof(double) * (size_t)(cand_lds_doubles(spb) + kGeoD * spb) : cand_geom_lds(spb));
-    };
-    if (step_waves && step_lds(step_waves, std::min(cg.spb, step_waves == 1 ? kStepWaveSpb : 16)) > 65536) step_waves = 0;
-    const int spb_f = std::min(cg.spb, step_waves == 1 ? kStepWaveSpb : 256 / 16);
-    const int64_t groups_f = (S + spb_f - 1) / spb_f;
-    const size_t lds_f = step_lds(step_waves, spb_f);
-    const bool step_fused = fused && M->n <= kLdsMapMax && lds_f <= 65536 && step_fused_on();
-    if (fio && (!step_fused || groups_f != 1)) return PP_ERR_STATE;
-    // the map lock is held from workspace binding through the (asynchronous) launches: a
-    // concurrent call cannot grow and free this stream's buffers in between
-    std::lock_guard<std::mutex> lk(M->mu);
-    int rc = dev_init(M, device);
-    if (rc) return rc;
-    DevState& DS = M->dev[device];
-    StreamWS& W = DS.sws[hip_stream];
-    rc = ensure_ws(W, st, Sv);
-    if (rc) return rc;
-    rc = ensure_gbits(W, st, cg.groups);
-    if (rc) return rc;
-    double* rec = nullptr;
-    uint64_t* adjm = nullptr;
-    if (ref_direct && !prm->emit_paths) {
-        rc = ensure_rec(W, st, S);
-        if (rc) return rc;
-        rec = rec_buf(W.rec);
-        adjm = adj_buf(W.rec, W.rec_cap);
-    }
-    // comfort mode without paths or draws, every scene's candidates in one block: k_cand makes the
-    // decision and stores the winner's spline slot in the record's memory (616 B per scene of its
-    // 3,088), k_winner_st re-runs the winner from it
-    double* wslot = nullptr;
-    // K0 (k_sort_cars) ahead of the one-lane K1: no car table, fewer than PP_SORT_DMAX draws, at
-    // most 16 rows per scene (k_prep's own sorting rule; larger tables keep the identity order)
-    SortedCars srt = {};
-    const int k0f = dbg(PP_DBG_SORT_CARS);
-    if ((k0f == 1 || (k0f == 0 && PP_SORT_K0)) && !in->tab_valid && Dn < PP_SORT_DMAX && in->car_stride >= 2 &&
-        in->car_stride <= 16 && prep_group(Sv) == 1) {
-        rc = ensure_srt(W, st, S, in->car_stride, srt);
-        if (rc) return rc;
-    }
-    size_t cand_lds = cg.lds;
-    if (PP_WSLOT && !ref_direct && !prm->emit_paths && cg.bps == 1 && Dn == 1) {
-        rc = ensure_rec(W, st, S);
-        if (rc) return rc;
-        wslot = rec_buf(W.rec);
-        cand_lds = ((cg.lds + 7) & ~(size_t)7) + sizeof(double) * 256;     // + sCost
-    }
-    if (dbg(PP_DBG_POISON)) {
-        // every call starts from NaN-filled (0xFF) intermediates and outputs, so no kernel can lean
-        // on what an earlier call left there (or on an output element it never writes); the
-        // slow-group bitmap must be all zero between calls (k_cand<true> clears what k_prep set)
-        auto fill = [&](void* p, size_t bytes) { return !p || !bytes || hipMemsetAsync(p, 0xFF, bytes, st) == hipSuccess; };
-        const int64_t Cn = (int64_t)Dn * NL * prm->n_speeds, N = prm->n_points;
-        const int64_t words = (cg.groups + 31) / 32;
-        std::vector<uint32_t> hb((size_t)words);
-        if (hipMemcpyAsync(hb.data(), W.gbits, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            return PP_ERR_HIP;
-        for (uint32_t w : hb)
-            if (w) return PP_ERR_STATE;
-        const bool ok = fill(W.ws, prep_bytes(W.ws_cap)) &&
-                        fill(W.rec, W.rec ? rec_bytes(W.rec_cap) : 0) &&
-                        fill(W.srt, W.srt ? W.srt_cap : 0) &&
-                        fill(W.gbits + W.gbits_cap + kPartMax, sizeof(uint32_t) * 32 * (size_t)W.gbits_cap) &&
-                        fill(out->winner, 4 * S) && fill(out->n_out, 4 * S) && fill(out->status, 4 * S) &&
-                        fill(out->next_x, 8 * N * S) && fill(out->next_y, 8 * N * S) &&
-                        fill(out->cost, 8 * Cn * S) && fill(out->info, sizeof(pp_scene_info) * S) &&
-                        fill(out->draw_mean_cost, Dn > 1 ? 8 * NL * prm->n_speeds * S : 0) &&
-                        fill(prm->emit_paths ? out->paths : nullptr, 16 * N * Cn * S) &&
-                        fill(prm->emit_paths ? out->path_len : nullptr, 4 * Cn * S);
-        if (!ok) return PP_ERR_HIP;
-    }
-    const PrepV pv = prep_bind(W.ws, W.ws_cap);
-    MapG mg;
-    mg.buf = DS.map;
-    mg.n = M->n;
-    mg.fastm = M->fastm;
-    mg.wg = M->wg;
-    mg.wg.cells = DS.wgrid;
-    mg.wseg = DS.wseg;
-    mg.atab = DS.atab;
-    // k_prep<true, false> stages the approach table after the map where both fit a block's 64 KB
-    mg.atab_lds = DS.atab && sizeof(double) * (((kMapArrays * (size_t)M->n + 1) & ~(size_t)1) + kAtabD * (size_t)M->n) <= 65536;
-    // tall: events at every kernel boundary; tk2: at K2's (PP_TIMING_K2 records only those two).
-    // The call's record is a group of 4 kPartMax slots (before K1, after K1, after K2, after
-    // K3/K4, per part); a slot takes an event from the pool when it is first recorded, so a
-    // K2-only call takes 2 events (2 per part when split) and an all-kernel call 4 per part
-    const bool timing = DS.timing != 0, tall = DS.timing == 1, tk2 = timing;
-    const size_t ev_base = DS.ev_rec.size();
-    if (timing) {
-        DS.ev_rec.resize(ev_base + 4 * kPartMax, nullptr);
-        DS.ev_kind.push_back((!(ref_direct && prm->emit_paths) && !emit_in ? 1 : 0) | (tall ? 0 : 16));
-    }
-    auto ev = [&](int i) -> hipEvent_t {
-        hipEvent_t& e = DS.ev_rec[ev_base + i];
-        if (!e) {
-            if (DS.ev_pool.empty() && hipEventCreate(&e) != hipSuccess) return nullptr;
-            if (!e) { e = DS.ev_pool.back(); DS.ev_pool.pop_back(); }
-        }
-        return e;
-    };
-    pp_params P = *prm;
-    pp_scene_batch B = *in;
-    pp_result R = *out;
-    if (!P.emit_paths) { R.paths = nullptr; R.path_len = nullptr; }
-    GroupBits gb = {};
-    gb.bits = W.gbits; gb.SPB = cg.spb; gb.BPS = cg.bps; gb.C = Cn_;
-    gb.count = W.gbits + W.gbits_cap;
-    gb.list = gb.count + kPartMax;
-#ifdef PP_CHECK
-    {   // checking builds: the bounds of every buffer this call's kernels store into
-        ChkLim L = {};
-        const long long Cn = (long long)Dn * NL * P.n_speeds;
-        L.paths = R.paths; L.npaths = R.paths ? (long long)S * P.n_points * Cn * 2 : 0;
-        L.nx = R.next_x; L.ny = R.next_y; L.nnext = (long long)S * P.n_points;
-        L.rec = rec; L.nrec = rec ? 3LL * PP_MAX_POINTS * W.rec_cap : 0;
-        L.adjm = (const unsigned long long*)adjm; L.nadj = adjm ? 2LL * W.rec_cap : 0;
-        L.cost = R.cost; L.ncost = (long long)S * Cn; L.nscen = S;
-        if (hipStreamSynchronize(st) != hipSuccess ||
-            hipMemcpyToSymbol(HIP_SYMBOL(g_lim), &L, sizeof L) != hipSuccess) return PP_ERR_HIP;
-    }
-#endif
-    if (step_fused) {
-        if (timing) DS.ev_kind.back() |= 32;          // (no K1 kernel: K1 runs inside the step)
-        if (tall) (void)hipEventRecord(ev(0), st);
-        // K1 takes 16 lanes for each of the block's spb_f scenes, K2 spb_f x C lanes: the block needs
-        // both (C <= 9 gives cg.threads < 16 spb_f; the K1 of the scenes beyond would not run)
-        const int threads_f = step_waves == 1 ? 256 : step_waves == 2 ? 512
-                                                      : std::max(cg.threads, ((16 * spb_f + 63) / 64) * 64);
-        // the step kernel's own start/end timestamps go into K2's events (the launch's dispatch
-        // records them): no marker packets in the stream, which cost a few us each in a ~0.1 ms step
-        hipEvent_t e1 = tk2 ? ev(1) : nullptr, e2 = tk2 ? ev(2) : nullptr;
-        if (fio) {
-            if (tk2) (void)hipEventRecord(ev(1), st);
-            hipLaunchKernelGGL(k_plan_frame, dim3(1), dim3(threads_f), lds_f, st, *fio, mg, B, P, pv, R, spb_f,
-                               rec, adjm, step_waves == 1 ? 1 : 0);
-            if (tk2) (void)hipEventRecord(ev(2), st);
-        } else if (step_waves == 2) {
-            hipExtLaunchKernelGGL(k_step_small512, dim3((unsigned)groups_f), dim3(threads_f), (uint32_t)lds_f, st,
-                                  e1, e2, 0u, mg, B, P, pv, R, spb_f, rec, adjm);
-        } else {
-            hipExtLaunchKernelGGL(k_step_small, dim3((unsigned)groups_f), dim3(threads_f), (uint32_t)lds_f, st,
-                                  e1, e2, 0u, mg, B, P, pv, R, spb_f, rec, adjm, step_waves == 1 ? 1 : 0);
-        }
-        if (tall) (void)hipEventRecord(ev(3), st);
-        if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-        return PP_OK;
-    }
-    if (hipMemsetAsync(gb.count, 0, kPartMax * sizeof(uint32_t), st) != hipSuccess) return PP_ERR_HIP;
-    const bool split = ref_direct && !P.emit_paths && !fused && cg.bps == 1 && Dn == 1 &&
-                       prep_group(Sv) == 1 && split_on(S);
-    g_dbg[PP_DBG_LAST_PARTS].store(1, std::memory_order_relaxed);
-    if (split) {
-        // NT = streams x chunks parts at group boundaries: part t takes groups [G t / NT, G (t + 1) /
-        // NT) and their scenes, on stream t % NS (stream 0: the caller's, else st2[.]); each part its
-        // own flagged-group list (count word t, its list from its first group's index on).
-        // Chunks run one after another (fork and join per chunk).
-        // Timing: each part's kernels by events on its own stream; pp_timing_read counts each stage
-        // once per call, as the span from a chunk's first part's start to its last part's end (the
-        // parts overlap, so one part's duration understates the stage's throughput), summed over
-        // the chunks.
-        const int NS = split_parts(S), NC = split_chunks(S), NT = NS * NC;
-        if (!W.fork && hipEventCreateWithFlags(&W.fork, hipEventDisableTiming) != hipSuccess) return PP_ERR_HIP;
-        for (int k = 0; k < NS - 1; k++)
-            if (!W.st2[k] && (hipStreamCreateWithFlags(&W.st2[k], hipStreamNonBlocking) != hipSuccess ||
-                              hipEventCreateWithFlags(&W.join[k], hipEventDisableTiming) != hipSuccess))
-                return PP_ERR_HIP;
-        const int64_t G = cg.groups;
-        const bool lmap = mg.n <= kLdsMapMax;
-        const size_t lds = lmap ? sizeof(double) * kMapArrays * (size_t)mg.n : 0;
-        const size_t lds_a = lmap && mg.atab_lds ? prep_lds_atab(mg.n) : lds;    // k_prep<true, false>
-        MapG mga = mg;
-        if (!mg.atab_lds) mga.atab = nullptr;
-        int launched = 0;     // parts launched (an empty part is skipped; never at >= 2,048 scenes)
-        for (int c = 0; c < NC; c++) {
-            // fork: the chunk's other streams start behind everything before it on the caller's stream
-            if (hipEventRecord(W.fork, st) != hipSuccess) return PP_ERR_HIP;
-            for (int k = 0; k < NS - 1; k++)
-                if (hipStreamWaitEvent(W.st2[k], W.fork, 0) != hipSuccess) return PP_ERR_HIP;
-            for (int h = 0; h < NS; h++) {
-                const int t = c * NS + h;
-                hipStream_t sh = h == 0 ? st : W.st2[h - 1];
-                const int64_t g0 = G * t / NT, g1 = G * (t + 1) / NT;
-                const int64_t v0 = std::min<int64_t>(S, g0 * cg.spb), v1 = std::min<int64_t>(S, g1 * cg.spb);
-                if (v1 <= v0) continue;
-                GroupBits gbh = gb;
-                gbh.count = gb.count + t;
-                gbh.list = gb.list + g0;
-                const int eh = 4 * launched++;
-                if (tall) (void)hipEventRecord(ev(eh), sh);
-                const unsigned pb = (unsigned)((v1 - v0 + 255) / 256);
-                if (srt.rows)         // (the split takes batches without draws: scene = evaluation)
-                    hipLaunchKernelGGL(k_sort_cars, dim3(pb), dim3(256), 0, sh, B, srt, v0, v1);
-                if (srt.rows) {
-                    if (prep_w4(v1 - v0, device)) {
-                        if (lmap) hipLaunchKernelGGL((k_prep<true, true, true>), dim3(pb), dim3(256), lds, sh, mg, B, P, pv, R.info, R.status, gbh, v0, v1, srt);
-                        else hipLaunchKernelGGL((k_prep<false, true, true>), dim3(pb), dim3(256), 0, sh, mg, B, P, pv, R.info, R.status, gbh, v0, v1, srt);
-                    } else {
-                        if (lmap) hipLaunchKernelGGL((k_prep<true, false, true>), dim3(pb), dim3(256), lds_a, sh, mga, B, P, pv, R.info, R.status, gbh, v0, v1, srt);
-                        else hipLaunchKernelGGL((k_prep<false, false, true>), dim3(pb), dim3(256), 0, sh, mg, B, P, pv, R.info, R.status, gbh, v0, v1, srt);
-                    }
-                } else if (prep_w4(v1 - v0, device)) {
-                    if (lmap) hipLaunchKernelGGL((k_prep<true, true>), dim3(pb), dim3(256), lds, sh, mg, B, P, pv, R.info, R.status, gbh, v0, v1, srt);
-                    else hipLaunchKernelGGL((k_prep<false, true>), dim3(pb), dim3(256), 0, sh, mg, B, P, pv, R.info, R.status, gbh, v0, v1, srt);
-                } else {
-                    if (lmap) hipLaunchKernelGGL((k_prep<true, false>), dim3(pb), dim3(256), lds_a, sh, mga, B, P, pv, R.info, R.status, gbh, v0, v1, srt);
-                    else hipLaunchKernelGGL((k_prep<false, false>), dim3(pb), dim3(256), 0, sh, mg, B, P, pv, R.info, R.status, gbh, v0, v1, srt);
-                }
-                if (tk2) (void)hipEventRecord(ev(eh + 1), sh);
-                const unsigned nsl = (unsigned)std::min<int64_t>(g1 - g0, 2048);
-                hipLaunchKernelGGL((k_cand<false, 1>), dim3((unsigned)(g1 - g0)), dim3(cg.threads), cg.lds, sh, mg, B, P, pv, R,
-                                   cg.spb, cg.bps, rec, adjm, W.gbits, G, gbh.list, gbh.count, g0, (double*)nullptr);
-                hipLaunchKernelGGL((k_cand<true, 1>), dim3(nsl), dim3(cg.threads), cg.lds, sh, mg, B, P, pv, R,
-                                   cg.spb, cg.bps, rec, adjm, W.gbits, G, gbh.list, gbh.count, g0, (double*)nullptr);
-                if (tk2) (void)hipEventRecord(ev(eh + 2), sh);
-                hipLaunchKernelGGL(k_emit<kEmitRows>, dim3((unsigned)((v1 - v0 + 255) / 256)), dim3(256), 0, sh, B, P, pv, R,
-                                   rec, adjm, v0, v1);
-                if (tall) (void)hipEventRecord(ev(eh + 3), sh);
-            }
-            // join: the caller's stream waits for the chunk's other streams
-            for (int k = 0; k < NS - 1; k++)
-                if (hipEventRecord(W.join[k], W.st2[k]) != hipSuccess || hipStreamWaitEvent(st, W.join[k], 0) != hipSuccess)
-                    return PP_ERR_HIP;
-        }
-        // (the timing record: parts launched, and parts per chunk for the per-chunk spans)
-        if (timing) DS.ev_kind.back() |= (launched << 8) | (NC > 1 ? NS << 16 : 0);
-        g_dbg[PP_DBG_LAST_PARTS].store(launched, std::memory_order_relaxed);
-        if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-        return PP_OK;
-    }
-    // K1: one lane per evaluation, or a group of G lanes per evaluation for small batches
-    {
-        const int threads = 256;
-        const int G = prep_group(Sv);
-        const int64_t blocks = (Sv * G + threads - 1) / threads;
-        if (tall) (void)hipEventRecord(ev(0), st);
-        const bool lmap = mg.n <= kLdsMapMax;
-        const size_t lds = lmap ? sizeof(double) * kMapArrays * (size_t)mg.n : 0;
-        const size_t lds_a = lmap && mg.atab_lds ? prep_lds_atab(mg.n) : lds;    // k_prep<true, false>
-        MapG mga = mg;
-        if (!mg.atab_lds) mga.atab = nullptr;
-#define PP_LAUNCH_PREP(KER) \
-        if (lmap) hipLaunchKernelGGL(KER<true>, dim3((unsigned)blocks), dim3(threads), lds, st, mg, B, P, pv, R.info, R.status, gb); \
-        else hipLaunchKernelGGL(KER<false>, dim3((unsigned)blocks), dim3(threads), 0, st, mg, B, P, pv, R.info, R.status, gb)
-        switch (G) {
-            case 2: { PP_LAUNCH_PREP(k_prep_g2); break; }
-            case 4: { PP_LAUNCH_PREP(k_prep_g4); break; }
-            case 8: { PP_LAUNCH_PREP(k_prep_g8); break; }
-            case 16: { PP_LAUNCH_PREP(k_prep_g16); break; }
-            default: {
-                if (srt.rows)
-                    hipLaunchKernelGGL(k_sort_cars, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, B, srt, (int64_t)0, S);
-                if (srt.rows) {
-                    if (prep_w4(Sv, device)) {
-                        if (lmap) hipLaunchKernelGGL((k_prep<true, true, true>), dim3((unsigned)blocks), dim3(threads), lds, st, mg, B, P, pv, R.info, R.status, gb, (int64_t)0, Sv, srt);
-                        else hipLaunchKernelGGL((k_prep<false, true, true>), dim3((unsigned)blocks), dim3(threads), 0, st, mg, B, P, pv, R.info, R.status, gb, (int64_t)0, Sv, srt);
-                    } else {
-                        if (lmap) hipLaunchKernelGGL((k_prep<true, false, true>), dim3((unsigned)blocks), dim3(threads), lds_a, st, mga, B, P, pv, R.info, R.status, gb, (int64_t)0, Sv, srt);
-                        else hipLaunchKernelGGL((k_prep<false, false, true>), dim3((unsigned)blocks), dim3(threads), 0, st, mg, B, P, pv, R.info, R.status, gb, (int64_t)0, Sv, srt);
-                    }
-                } else if (prep_w4(Sv, device)) {
-                    if (lmap) hipLaunchKernelGGL((k_prep<true, true>), dim3((unsigned)blocks), dim3(threads), lds, st, mg, B, P, pv, R.info, R.status, gb, (int64_t)0, Sv, srt);
-                    else hipLaunchKernelGGL((k_prep<false, true>), dim3((unsigned)blocks), dim3(threads), 0, st, mg, B, P, pv, R.info, R.status, gb, (int64_t)0, Sv, srt);
-                } else {
-                    if (lmap) hipLaunchKernelGGL((k_prep<true, false>), dim3((unsigned)blocks), dim3(threads), lds_a, st, mga, B, P, pv, R.info, R.status, gb, (int64_t)0, Sv, srt);
-                    else hipLaunchKernelGGL((k_prep<false, false>), dim3((unsigned)blocks), dim3(threads), 0, st, mg, B, P, pv, R.info, R.status, gb, (int64_t)0, Sv, srt);
-                }
-                break;
-            }
-        }
-#undef PP_LAUNCH_PREP
-    }
-    // K2 (+ K4 for small batches in reference mode: k_cand_small)
-    {
-        const unsigned nb = (unsigned)cg.groups;
-        const unsigned nslow = (unsigned)std::min<int64_t>(cg.groups, 2048);
-        const int64_t ng = cg.groups;
-        if (tk2) (void)hipEventRecord(ev(1), st);
-#define PP_LAUNCH_CAND(MODE)                                                                              \
-        hipLaunchKernelGGL((k_cand<false, MODE>), dim3(nb), dim3(cg.threads), cand_lds, st, mg, B, P, pv, R, \
-                           cg.spb, cg.bps, rec, adjm, W.gbits, ng, gb.list, gb.count, (int64_t)0, wslot);   \
-        hipLaunchKernelGGL((k_cand<true, MODE>), dim3(nslow), dim3(cg.threads), cand_lds, st, mg, B, P, pv, R, \
-                           cg.spb, cg.bps, rec, adjm, W.gbits, ng, gb.list, gb.count, (int64_t)0, wslot)
-        if (P.emit_paths) { PP_LAUNCH_CAND(2); }
-        else if (ref_direct && fused) {
-            hipLaunchKernelGGL(k_cand_small, dim3(nb), dim3(cg.threads), cg.lds, st, mg, B, P, pv, R,
-                               cg.spb, rec, adjm, W.gbits);
-        }
-        else if (ref_direct) { PP_LAUNCH_CAND(1); }
-        else { PP_LAUNCH_CAND(0); }
-#undef PP_LAUNCH_CAND
-    }
-    if (tk2) (void)hipEventRecord(ev(2), st);
-    // K4 (reference mode, winner-only output): replay the winners' recorded paths
-    if (ref_direct && !P.emit_paths && !emit_in) {
-        if (S <= kEmitSmall) {     // latency regime: 64-lane blocks over more CUs, 16 steps per load round
-            const int64_t blocks = (S + 63) / 64;
-            hipLaunchKernelGGL(k_emit<16>, dim3((unsigned)blocks), dim3(64), 0, st, B, P, pv, R, rec, adjm, (int64_t)0, S);
-        } else {
-            const int64_t blocks = (S + 255) / 256;
-            hipLaunchKernelGGL(k_emit<kEmitRows>, dim3((unsigned)blocks), dim3(256), 0, st, B, P, pv, R, rec, adjm, (int64_t)0, S);
-        }
-    }
-    // K3 (comfort mode, or any mode with draws): argmin + winner path
-    if (!ref_direct) {
-        const int64_t blocks = (S + kWinBlock - 1) / kWinBlock;
-        if (wslot) {
-            const unsigned b256 = (unsigned)((S + 255) / 256);
-            hipLaunchKernelGGL((k_winner_st<false>), dim3(b256), dim3(256), 0, st, B, P, pv, R, (const double*)wslot);
-            hipLaunchKernelGGL((k_winner_st<true>), dim3(b256), dim3(256), 0, st, B, P, pv, R, (const double*)wslot);
-        } else {
-            hipLaunchKernelGGL((k_winner<false>), dim3((unsigned)blocks), dim3(kWinBlock), 0, st, mg, B, P, pv, R);
-            hipLaunchKernelGGL((k_winner<true>), dim3((unsigned)blocks), dim3(kWinBlock), 0, st, mg, B, P, pv, R);
-        }
-    }
-    if (tall) (void)hipEventRecord(ev(3), st);
-    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-    return PP_OK;
-}
-
-}  // namespace
-extern "C" {
-
-int32_t pp_eval(pp_map* M, const pp_scene_batch* in, const pp_params* prm, pp_result* out,
-                int32_t device, void* hip_stream) {
-    return eval_impl(M, in, prm, out, device, hip_stream, nullptr);
-}
-
-int32_t pp_debug_set(int32_t key, int32_t value) {
-    bool ok = false;
-    switch (key) {
-        case PP_DBG_PREP_GROUP: ok = prep_group_ok(value); break;
-        case PP_DBG_PREP_WAVES: ok = value == 0 || value == 3 || value == 4; break;
-        case PP_DBG_SHAPE: ok = value >= 0 && value <= PP_SHAPE_STEP; break;
-        case PP_DBG_POISON: ok = value == 0 || value == 1; break;
-        case PP_DBG_SPLIT: ok = value >= 0 && value <= 2; break;
-        case PP_DBG_SORT_CARS: ok = value >= 0 && value <= 2; break;
-        default: break;       // (PP_DBG_LAST_PARTS is read-only)
-    }
-    if (!ok) return PP_ERR_ARG;
-    g_dbg[key].store(value, std::memory_order_relaxed);
-    return PP_OK;
-}
-
-int32_t pp_debug_get(int32_t key) { return key >= 0 && key < PP_DBG_KEYS ? dbg(key) : PP_ERR_ARG; }
-
-int32_t pp_timing_enable(pp_map* M, int32_t device, int32_t enable) {
-    if (!M || device < 0 || device >= kMaxDev) return PP_ERR_ARG;
-    std::lock_guard<std::mutex> lk(M->mu);
-    DevState& D = M->dev[device];
-    D.timing = enable == PP_TIMING_K2 ? 2 : (enable != 0 ? 1 : 0);
-    if (D.timing) {
-        // events made now, outside any timed region: 2,048 calls of K2-only timing (2 events each,
-        // 2 per part when split) or 1,024 of all-kernel timing (4 per part); pp_eval takes the
-        // events it records from this pool, pp_timing_read returns them
-        DeviceGuard g(device);
-        const int rc = dev_init(M, device);       // (pp_map_destroy frees the events of initialised devices)
-        if (rc) return rc;
-        while (D.ev_pool.size() + D.ev_rec.size() < 4 * kSplitMax * 256) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return PP_ERR_HIP;
-            D.ev_pool.push_back(e);
-        }
-    }
-    return PP_OK;
-}
-
-int32_t pp_timing_read(pp_map* M, int32_t device, double* ms3, int64_t* launches3) {
-    if (!M || device < 0 || device >= kMaxDev || !ms3 || !launches3) return PP_ERR_ARG;
-    std::lock_guard<std::mutex> lk(M->mu);
-    DevState& D = M->dev[device];
-    DeviceGuard g(device);
-    for (int k = 0; k < 3; k++) { ms3[k] = 0; launches3[k] = 0; }
-    int rc = PP_OK;
-    constexpr int EG = 4 * kPartMax;
-    const size_t ng = D.ev_rec.size() / EG;
-    // signed milliseconds from a to b (either order)
-    auto dt = [&](hipEvent_t a, hipEvent_t b, float& t) {
-        if (!a || !b) { rc = PP_ERR_HIP; return false; }
-        if (hipEventElapsedTime(&t, a, b) == hipSuccess) return true;
-        if (hipEventElapsedTime(&t, b, a) == hipSuccess) { t = -t; return true; }
-        rc = PP_ERR_HIP;
-        return false;
-    };
-    for (size_t i = 0; i < ng; i++) {
-        const int kind = D.ev_kind[i], parts = (kind >> 8) & 0xFF, np = parts ? parts : 1;
-        const int per = (kind >> 16) & 0xF, pc = per ? per : np;    // parts per chunk
-        const bool k2only = (kind & 16) != 0;
-        hipEvent_t* e0 = &D.ev_rec[EG * i];
-        for (int h = 0; h < np; h++) {
-            hipEvent_t last = k2only ? e0[4 * h + 2] : e0[4 * h + 3];
-            if (!last || hipEventSynchronize(last) != hipSuccess) rc = PP_ERR_HIP;
-        }
-        // stage k (0: K1, 1: K2, 2: K3/K4) of a call: per chunk, from its earliest start to its
-        // latest end over the chunk's parts (one stream: the kernel's own interval; a split call's
-        // parts overlap, and the stage's time is the span they cover together, as in a kernel
-        // trace), summed over the chunks; one launch per call
-        for (int k = 0; k < 3; k++) {
-            if (k != 1 && (k2only || (k == 0 && (kind & 32)) || (k == 2 && !(kind & 1)))) continue;
-            float sum = 0;
-            bool ok = true;
-            for (int c0 = 0; c0 < np && ok; c0 += pc) {
-                float lo = 0, hi = 0;
-                for (int h = c0; h < std::min(np, c0 + pc) && ok; h++) {
-                    float a, b;
-                    ok = dt(e0[1], e0[4 * h + k], a) && dt(e0[1], e0[4 * h + k + 1], b);
-                    if (ok) { lo = h == c0 ? a : std::min(lo, a); hi = h == c0 ? b : std::max(hi, b); }
-                }
-                sum += hi - lo;
-            }
-            if (ok) { ms3[k] += sum; launches3[k]++; }
-        }
-        for (int k = 0; k < EG; k++)
-            if (D.ev_rec[EG * i + k]) D.ev_pool.push_back(D.ev_rec[EG * i + k]);
-    }
-    D.ev_rec.clear();
-    D.ev_kind.clear();
-    return rc;
-}
-
-int32_t pp_synth_scenes(pp_map* M, uint64_t seed, int64_t first_scene, pp_scene_batch* out,
-                        int32_t device, void* hip_stream) {
-    if (!M || !out || device < 0 || device >= kMaxDev || out->n_scenes < 0 || first_scene < 0) return PP_ERR_ARG;
-    if (out->car_stride < ppsynth::kSynthCars) return PP_ERR_ARG;
-    if (out->n_scenes == 0) return PP_OK;
-    DeviceGuard g(device);
-    ppsynth::LaneTables T;
-    {
-        std::lock_guard<std::mutex> lk(M->mu);
-        const int rc = dev_init(M, device);
-        if (rc) return rc;
-        T = lane_tables(M->dev[device].lanetab, M->n);
-    }
-    const ppsynth::OutBatch o = out_batch(out);
-    const int threads = 256;
-    const int64_t blocks = (o.S + threads - 1) / threads;
-    hipLaunchKernelGGL(k_synth, dim3((unsigned)blocks), dim3(threads), 0, (hipStream_t)hip_stream, T, seed, first_scene, o);
-    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-    return PP_OK;
-}
-
-int32_t pp_synth_scenes_host(const pp_map* M, uint64_t seed, int64_t first_scene, pp_scene_batch* out) {
-    if (!M || !out || out->n_scenes < 0 || first_scene < 0 || out->car_stride < ppsynth::kSynthCars) return PP_ERR_ARG;
-    const ppsynth::LaneTables T = lane_tables(M->lanetab.data(), M->n);
-    const ppsynth::OutBatch o = out_batch(out);
-    for (int64_t s = 0; s < o.S; s++) ppsynth::synth_scene(T, seed, first_scene + s, s, o);
-    return PP_OK;
-}
-
-int32_t pp_synth_traffic(pp_map* M, uint64_t seed, int64_t first_scene, pp_scene_batch* tel,
-                         pp_traffic* out, int32_t device, void* hip_stream) {
-    if (!M || !tel || device < 0 || device >= kMaxDev || tel->n_scenes < 0 || first_scene < 0 ||
-        tel->car_stride < ppsynth::kSynthCars || !traffic_ok(out, tel) ||
-        (tel->tab_valid && (tel->tab_slots < ppsynth::kSynthCars || tel->tab_slots > PP_MAX_CARS)))
-        return PP_ERR_ARG;
-    if (tel->n_scenes == 0) return PP_OK;
-    DeviceGuard g(device);
-    ppsynth::LaneTables T;
-    {
-        std::lock_guard<std::mutex> lk(M->mu);
-        const int rc = dev_init(M, device);
-        if (rc) return rc;
-        T = lane_tables(M->dev[device].lanetab, M->n);
-    }
-    out->n_cars = ppsynth::kSynthCars;
-    const ppsynth::OutBatch o = out_batch(tel);
-    const int64_t blocks = (o.S + 255) / 256;
-    hipLaunchKernelGGL(k_synth_traffic, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, T,
-                       seed, first_scene, o, traffic_view(out, o.S), *tel);
-    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-    return PP_OK;
-}
-
-int32_t pp_synth_traffic_host(const pp_map* M, uint64_t seed, int64_t first_scene, pp_scene_batch* tel,
-                              pp_traffic* out) {
-    if (!M || !tel || tel->n_scenes < 0 || first_scene < 0 || tel->car_stride < ppsynth::kSynthCars ||
-        !traffic_ok(out, tel) ||
-        (tel->tab_valid && (tel->tab_slots < ppsynth::kSynthCars || tel->tab_slots > PP_MAX_CARS)))
-        return PP_ERR_ARG;
-    const ppsynth::LaneTables T = lane_tables(M->lanetab.data(), M->n);
-    out->n_cars = ppsynth::kSynthCars;
-    const ppsynth::OutBatch o = out_batch(tel);
-    const ppsynth::TrafficV tv = traffic_view(out, o.S);
-    for (int64_t s = 0; s < o.S; s++) {
-        ppsynth::synth_scene(T, seed, first_scene + s, s, o, &tv);
-        for (int j = 0; tel->tab_valid && j < tel->tab_slots; j++) {
-            tel->tab_valid[(int64_t)j * o.S + s] = 0;
-            if (tel->tab_id) tel->tab_id[(int64_t)j * o.S + s] = j;
-        }
-    }
-    return PP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-void launch_judge(const ppsynth::LaneTables& T, const pp_scene_batch* tel, const ppsynth::TrafficV& tv,
-                  const pp_result* plan, int32_t consume, const pp_judge_cfg* jc, const pp_judge* js,
-                  hipStream_t stream) {
-    const int64_t S = tel->n_scenes;
-    hipLaunchKernelGGL(k_judge, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, stream, T, S, tel->ego_x,
-                       tel->ego_y, tel->ego_yaw_deg, plan->next_x, plan->next_y, plan->n_out, tv, consume, *jc, *js);
-}
-
-void launch_follow(const ppsynth::LaneTables& T, const ppfollow::ArcTables& AT, const pp_scene_batch* tel,
-                   const ppsynth::TrafficV& tv, int32_t consume, const pp_follow_cfg* fc, const pp_follow* fs,
-                   hipStream_t stream) {
-    const int64_t S = tel->n_scenes;
-    hipLaunchKernelGGL(k_follow, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, stream, T, AT, S, tel->ego_x,
-                       tel->ego_y, tel->ego_speed_mph, tv, consume, *fc, *fs);
-}
-
-// pp_rollout's loop; with follow state (fc, fs non-null) k_follow runs after pp_eval, with a judge (jc,
-// js non-null) k_judge runs before k_sim
-int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
-                     const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
-                     void* hip_stream, const pp_judge_cfg* jc, const pp_judge* js,
-                     const pp_follow_cfg* fc = nullptr, const pp_follow* fs = nullptr) {
-    if (!M || !tel || !prm || !cfg || !res || device < 0 || device >= kMaxDev || !traffic_ok(traffic, tel))
-        return PP_ERR_ARG;
-    if (cfg->n_frames < 0 || cfg->consume < 1 || !(cfg->sensor_range >= 0) || prm->n_draws > 1 ||
-        prm->emit_paths || !tel->tab_valid || !tel->tab_lane || !tel->tab_s || !tel->tab_d ||
-        !tel->tab_vs || !tel->tab_vd || !tel->tab_vx || !tel->tab_vy || tel->car_stride < traffic->n_cars ||
-        tel->tab_slots < traffic->n_cars)
-        return PP_ERR_ARG;
-    if (log && log->plan_x && !log->plan_y) return PP_ERR_ARG;
-    if (tel->n_scenes == 0 || cfg->n_frames == 0) return PP_OK;
-    DeviceGuard g(device);
-    ppsynth::LaneTables T;
-    ppfollow::ArcTables AT = {nullptr, nullptr};
-    {
-        std::lock_guard<std::mutex> lk(M->mu);
-        const int rc = dev_init(M, device);
-        if (rc) return rc;
-        T = lane_tables(M->dev[device].lanetab, M->n);
-        if (fs) {
-            const int ra = arc_init(M, device);
-            if (ra) return ra;
-            AT = ppfollow::arc_tables(M->dev[device].arctab, M->n);
-        }
-    }
-    SimArgs A;
-    A.consume = cfg->consume;
-    A.range2 = cfg->sensor_range * cfg->sensor_range;
-    if (log) A.log = *log; else memset(&A.log, 0, sizeof(A.log));
-    const ppsynth::TrafficV tv = traffic_view(traffic, tel->n_scenes);
-    const int64_t blocks = (tel->n_scenes + 255) / 256;
-    for (int f = 0; f < cfg->n_frames; f++) {
-        const int rc = pp_eval(M, tel, prm, res, device, hip_stream);
-        if (rc != PP_OK) return rc;
-        if (fs) {
-            launch_follow(T, AT, tel, tv, cfg->consume, fc, fs, (hipStream_t)hip_stream);
-            if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-        }
-        if (js) {
-            launch_judge(T, tel, tv, res, cfg->consume, jc, js, (hipStream_t)hip_stream);
-            if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-        }
-        A.frame = f;
-        hipLaunchKernelGGL(k_sim, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, T, *tel,
-                           tv, *prm, *res, A);
-        if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-    }
-    return PP_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int32_t pp_rollout(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
-                   const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
-                   void* hip_stream) {
-    return rollout_loop(M, tel, traffic, prm, cfg, res, log, device, hip_stream, nullptr, nullptr);
-}
-
-int32_t pp_rollout_judged(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
-                          const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
-                          void* hip_stream, const pp_judge_cfg* jcfg, pp_judge* state) {
-    if (!judge_ok(jcfg, state) || !cfg || !judge_frame_ok(tel, traffic, res, cfg->consume)) return PP_ERR_ARG;
-    return rollout_loop(M, tel, traffic, prm, cfg, res, log, device, hip_stream, jcfg, state);
-}
-
-void pp_judge_cfg_default(pp_judge_cfg* c) {
-    if (!c) return;
-    memset(c, 0, sizeof(*c));
-    c->speed_limit_mph = 50;
-    c->max_acc = 10;
-    c->max_jerk = 10;
-    c->ego_length = c->car_length = 4.5;
-    c->ego_width = c->car_width = 2.0;
-    c->lane_tol = 1.0;
-    c->acc_window = 10;
-    c->jerk_window = 50;
-    c->off_lane_steps = 150;
-}
-
-int32_t pp_judge_frame(pp_map* M, const pp_scene_batch* tel, const pp_traffic* traffic, const pp_result* plan,
-                       int32_t consume, const pp_judge_cfg* cfg, pp_judge* state, int32_t device,
-                       void* hip_stream) {
-    if (!M || device < 0 || device >= kMaxDev || !judge_ok(cfg, state) ||
-        !judge_frame_ok(tel, traffic, plan, consume))
-        return PP_ERR_ARG;
-    if (tel->n_scenes == 0) return PP_OK;
-    DeviceGuard g(device);
-    ppsynth::LaneTables T;
-    {
-        std::lock_guard<std::mutex> lk(M->mu);
-        const int rc = dev_init(M, device);
-        if (rc) return rc;
-        T = lane_tables(M->dev[device].lanetab, M->n);
-    }
-    launch_judge(T, tel, traffic_view(traffic, tel->n_scenes), plan, consume, cfg, state, (hipStream_t)hip_stream);
-    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-    return PP_OK;
-}
-
-int32_t pp_judge_frame_host(const pp_map* M, const pp_scene_batch* tel, const pp_traffic* traffic,
-                            const pp_result* plan, int32_t consume, const pp_judge_cfg* cfg, pp_judge* state) {
-    if (!M || !judge_ok(cfg, state) || !judge_frame_ok(tel, traffic, plan, consume)) return PP_ERR_ARG;
-    const ppsynth::LaneTables T = lane_tables(M->lanetab.data(), M->n);
-    const int64_t S = tel->n_scenes;
-    const ppsynth::TrafficV tv = traffic_view(traffic, S);
-    for (int64_t s = 0; s < S; s++)
-        ppjudge::judge_scene(T, S, s, tel->ego_x[s], tel->ego_y[s], tel->ego_yaw_deg[s], plan->next_x, plan->next_y,
-                             plan->n_out[s], tv, consume, *cfg, *state);
-    return PP_OK;
-}
-
-int32_t pp_rollout_reactive(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
-                            const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
-                            void* hip_stream, const pp_judge_cfg* jcfg, pp_judge* jstate,
-                            const pp_follow_cfg* fcfg, pp_follow* fstate) {
-    if (!follow_ok(fcfg, fstate) || !cfg || !follow_frame_ok(tel, traffic, cfg->consume)) return PP_ERR_ARG;
-    if (jstate && (!judge_ok(jcfg, jstate) || !judge_frame_ok(tel, traffic, res, cfg->consume))) return PP_ERR_ARG;
-    return rollout_loop(M, tel, traffic, prm, cfg, res, log, device, hip_stream, jstate ? jcfg : nullptr, jstate,
-                        fcfg, fstate);
-}
-
-void pp_follow_cfg_default(pp_follow_cfg* c) {
-    if (!c) return;
-    memset(c, 0, sizeof(*c));
-    c->max_acc = 2.0;
-    c->comfort_brake = 3.0;
-    c->max_brake = 8.0;
-    c->time_headway = 1.2;
-    c->min_gap = 2.0;
-    c->gap_floor = 0.5;
-    c->horizon = 150;
-    c->car_length = c->ego_length = 4.5;
-    c->lateral_reach = 2.0;
-    c->react_to_ego = 1;
-}
-
-int32_t pp_traffic_follow(pp_map* M, const pp_scene_batch* tel, pp_traffic* traffic, int32_t consume,
-                          const pp_follow_cfg* cfg, pp_follow* state, int32_t device, void* hip_stream) {
-    if (!M || device < 0 || device >= kMaxDev || !follow_ok(cfg, state) || !follow_frame_ok(tel, traffic, consume))
-        return PP_ERR_ARG;
-    if (tel->n_scenes == 0) return PP_OK;
-    DeviceGuard g(device);
-    ppsynth::LaneTables T;
-    ppfollow::ArcTables AT;
-    {
-        std::lock_guard<std::mutex> lk(M->mu);
-        int rc = dev_init(M, device);
-        if (rc) return rc;
-        rc = arc_init(M, device);
-        if (rc) return rc;
-        T = lane_tables(M->dev[device].lanetab, M->n);
-        AT = ppfollow::arc_tables(M->dev[device].arctab, M->n);
-    }
-    launch_follow(T, AT, tel, traffic_view(traffic, tel->n_scenes), consume, cfg, state, (hipStream_t)hip_stream);
-    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-    return PP_OK;
-}
-
-int32_t pp_traffic_follow_host(const pp_map* M, const pp_scene_batch* tel, pp_traffic* traffic, int32_t consume,
-                               const pp_follow_cfg* cfg, pp_follow* state) {
-    if (!M || !follow_ok(cfg, state) || !follow_frame_ok(tel, traffic, consume)) return PP_ERR_ARG;
-    const ppsynth::LaneTables T = lane_tables(M->lanetab.data(), M->n);
-    const ppfollow::ArcTables AT = ppfollow::arc_tables(M->arctab.data(), M->n);
-    const int64_t S = tel->n_scenes;
-    const ppsynth::TrafficV tv = traffic_view(traffic, S);
-    for (int64_t s = 0; s < S; s++)
-        ppfollow::follow_scene(T, AT, S, s, tel->ego_x[s], tel->ego_y[s], tel->ego_speed_mph[s], tv, consume, *cfg,
-                               *state);
-    return PP_OK;
-}
-
-// Host-memory batch (the batched onMessage): stage the scenes (and their car table) into device
-// memory, pp_eval, copy results (and the updated table) back. Synchronous.
-// pp_plan_batch_host stages batches up to this many scenes through its pinned mirror
-constexpr int64_t kStageMirrorMax = 512;
-int32_t pp_plan_batch_host(pp_map* M, int32_t device, pp_scene_batch* hin, const pp_params* prm,
-                           pp_result* hout, void* hip_stream) {
-    if (!M || !hin || !prm || !hout || device < 0 || device >= kMaxDev || !params_ok(prm) || prm->emit_paths ||
-        hin->n_scenes < 0 || hin->car_stride < 0 || hin->car_stride > PP_MAX_CARS)
-        return PP_ERR_ARG;
-    if (!hout->winner || !hout->n_out || !hout->next_x || !hout->next_y || !hout->cost || !hout->status)
-        return PP_ERR_ARG;
-    const int64_t S = hin->n_scenes;
-    if (S == 0) return PP_OK;
-    const int J = hin->car_stride, N = prm->n_points;
-    const int C = n_draws(prm) * NL * prm->n_speeds;
-    const bool tab = hin->tab_valid != nullptr;
-    // staging layout: doubles first, then 4-byte fields
-    const int TS = tab ? hin->tab_slots : 0;
-    if (tab && (TS < 0 || TS > PP_MAX_CARS)) return PP_ERR_ARG;
-    // every host pointer the staging copies touch (small batches memcpy them on the host, so a
-    // NULL here must be refused before staging, not left to the copy)
-    if (!hin->ego_x || !hin->ego_y || !hin->ego_yaw_deg || !hin->ego_speed_mph || !hin->prev_x || !hin->prev_y ||
-        !hin->n_prev || !hin->prev_target_lane || !hin->n_cars)
-        return PP_ERR_ARG;
-    if (J > 0 && (!hin->car_id || !hin->car_x || !hin->car_y || !hin->car_vx || !hin->car_vy)) return PP_ERR_ARG;
-    if (tab && TS > 0 && (!hin->tab_lane || !hin->tab_s || !hin->tab_d || !hin->tab_vs || !hin->tab_vd ||
-                          !hin->tab_vx || !hin->tab_vy))
-        return PP_ERR_ARG;
-    const size_t nd = (size_t)S * (4 + 2 * PP_PREV_KEEP + 4 * J + 6 * TS + 2 * N + C);
-    const size_t ni = (size_t)S * (3 + J + 3 * TS + 3);
-    const size_t bytes = nd * 8 + ni * 4 + 256;
-    DeviceGuard g(device);
-    hipStream_t st = (hipStream_t)hip_stream;
-    std::lock_guard<std::mutex> stage_lock(M->dev[device].stage_mu);
-    char* base;
-    char* mirror;                 // pinned host mirror of the staging buffer (same offsets)
-    {
-        std::lock_guard<std::mutex> lk(M->mu);
-        int rc = dev_init(M, device);
-        if (rc) return rc;
-        DevState& D = M->dev[device];
-        if (D.stage_cap < bytes) {
-            if (D.stage) { (void)hipDeviceSynchronize(); (void)hipFree(D.stage); D.stage = nullptr; D.stage_cap = 0; }
-            if (D.stage_host) { (void)hipHostFree(D.stage_host); D.stage_host = nullptr; }
-            if (hipMalloc(&D.stage, bytes) != hipSuccess) return PP_ERR_NOMEM;
-            if (hipHostMalloc(&D.stage_host, bytes, hipHostMallocDefault) != hipSuccess) {
-                (void)hipFree(D.stage); D.stage = nullptr; return PP_ERR_NOMEM;
-            }
-            D.stage_cap = bytes;
-        }
-        base = (char*)D.stage;
-        mirror = (char*)D.stage_host;
-    }
-    double* dp = (double*)base;
-    int32_t* ip = (int32_t*)(base + nd * 8);
-    auto takeD = [&](size_t n) { double* r = dp; dp += n; return r; };
-    auto takeI = [&](size_t n) { int32_t* r = ip; ip += n; return r; };
-    bool ok = true;
-    // Small batches (latency): inputs are gathered into the pinned mirror; the input fields lead
-    // each region (doubles, then ints), so one copy per region moves them, and one per region
-    // brings the outputs back. Large batches (bandwidth): one asynchronous copy per field straight
-    // from and to the caller's buffers (the extra host memcpy through the mirror costs more there).
-    const bool small = S <= kStageMirrorMax;
-    auto h2d = [&](void* d, const void* h, size_t n) {
-        if (!n) return;
-        if (small) memcpy(mirror + ((char*)d - base), h, n);
-        else if (hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, st) != hipSuccess) ok = false;
-    };
-    pp_scene_batch B;
-    memset(&B, 0, sizeof(B));
-    B.n_scenes = S; B.car_stride = J;
-    double* ego = takeD(4 * S);
-    B.ego_x = ego; B.ego_y = ego + S; B.ego_yaw_deg = ego + 2 * S; B.ego_speed_mph = ego + 3 * S;
-    h2d(ego, hin->ego_x, 8 * S); h2d(ego + S, hin->ego_y, 8 * S);
-    h2d(ego + 2 * S, hin->ego_yaw_deg, 8 * S); h2d(ego + 3 * S, hin->ego_speed_mph, 8 * S);
-    double* pxy = takeD(2 * PP_PREV_KEEP * S);
-    B.prev_x = pxy; B.prev_y = pxy + PP_PREV_KEEP * S;
-    h2d(pxy, hin->prev_x, 8 * PP_PREV_KEEP * S); h2d(pxy + PP_PREV_KEEP * S, hin->prev_y, 8 * PP_PREV_KEEP * S);
-    double* cars = takeD(4 * (size_t)J * S);
-    B.car_x = cars; B.car_y = cars + J * S; B.car_vx = cars + 2 * J * S; B.car_vy = cars + 3 * J * S;
-    if (J) {
-        h2d(cars, hin->car_x, 8 * J * S); h2d(cars + J * S, hin->car_y, 8 * J * S);
-        h2d(cars + 2 * J * S, hin->car_vx, 8 * J * S); h2d(cars + 3 * J * S, hin->car_vy, 8 * J * S);
-    }
-    double* tabd = nullptr;
-    if (tab) {
-        tabd = takeD(6 * (size_t)TS * S);
-        const double* src[6] = {hin->tab_s, hin->tab_d, hin->tab_vs, hin->tab_vd, hin->tab_vx, hin->tab_vy};
-        double** dst[6] = {&B.tab_s, &B.tab_d, &B.tab_vs, &B.tab_vd, &B.tab_vx, &B.tab_vy};
-        for (int k = 0; k < 6; k++) { *dst[k] = tabd + k * (size_t)TS * S; h2d(*dst[k], src[k], 8 * (size_t)TS * S); }
-        B.tab_slots = TS;
-    }
-    double* nxy = takeD(2 * (size_t)N * S);
-    double* cost = takeD((size_t)C * S);
-    int32_t* ints = takeI(3 * S);
-    B.n_prev = ints; B.prev_target_lane = ints + S; B.n_cars = ints + 2 * S;
-    h2d(ints, hin->n_prev, 4 * S); h2d(ints + S, hin->prev_target_lane, 4 * S); h2d(ints + 2 * S, hin->n_cars, 4 * S);
-    int32_t* cid = takeI((size_t)J * S);
-    B.car_id = cid;
-    h2d(cid, hin->car_id, 4 * J * S);
-    int32_t* tabi = nullptr;
-    if (tab) {
-        tabi = takeI(3 * (size_t)TS * S);
-        B.tab_valid = tabi; B.tab_lane = tabi + (size_t)TS * S;
-        h2d(tabi, hin->tab_valid, 4 * (size_t)TS * S); h2d(tabi + (size_t)TS * S, hin->tab_lane, 4 * (size_t)TS * S);
-        if (hin->tab_id) { B.tab_id = tabi + 2 * (size_t)TS * S; h2d(B.tab_id, hin->tab_id, 4 * (size_t)TS * S); }
-    }
-    int32_t* outi = takeI(3 * S);
-    pp_result R;
-    memset(&R, 0, sizeof(R));
-    R.winner = outi; R.n_out = outi + S; R.status = (uint32_t*)(outi + 2 * S);
-    R.next_x = nxy; R.next_y = nxy + (size_t)N * S; R.cost = cost;
-    const char* d_in_end = (const char*)nxy;           // doubles: inputs [base, nxy)
-    const char* i_beg = base + nd * 8;                  // ints: inputs [i_beg, outi)
-    const char* d_out_beg = tab ? (const char*)tabd : (const char*)nxy;   // outputs: (tables,) plans, costs
-    const char* d_out_end = (const char*)(cost + (size_t)C * S);
-    const char* i_out_beg = tab ? (const char*)tabi : (const char*)outi;
-    const char* i_out_end = (const char*)(outi + 3 * S);
-    auto copy = [&](const char* lo, const char* hi, bool in) {
-        if (hi <= lo) return;
-        char* h = mirror + (lo - base);
-        if (hipMemcpyAsync(in ? (void*)lo : (void*)h, in ? (const void*)h : (const void*)lo, (size_t)(hi - lo),
-                           in ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, st) != hipSuccess) ok = false;
-    };
-    if (small) { copy(base, d_in_end, true); copy(i_beg, (const char*)outi, true); }
-    if (!ok) return PP_ERR_HIP;
-    int rc = pp_eval(M, &B, prm, &R, device, hip_stream);
-    if (rc != PP_OK) return rc;
-    if (small && dbg(PP_DBG_POISON)) {   // the mirror's pure-output regions (inputs may still be in flight)
-        memset(mirror + ((const char*)nxy - base), 0xFF, (size_t)(d_out_end - (const char*)nxy));
-        memset(mirror + ((const char*)outi - base), 0xFF, (size_t)(i_out_end - (const char*)outi));
-    }
-    if (small) {
-        copy(d_out_beg, d_out_end, false);
-        copy(i_out_beg, i_out_end, false);
-        if (!ok || hipStreamSynchronize(st) != hipSuccess) return PP_ERR_HIP;
-    }
-    auto d2h = [&](void* h, const void* d, size_t n) {
-        if (!n) return;
-        if (small) memcpy(h, mirror + ((const char*)d - base), n);
-        else if (hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, st) != hipSuccess) ok = false;
-    };
-    d2h(hout->winner, R.winner, 4 * S); d2h(hout->n_out, R.n_out, 4 * S); d2h(hout->status, R.status, 4 * S);
-    d2h(hout->next_x, R.next_x, 8 * (size_t)N * S); d2h(hout->next_y, R.next_y, 8 * (size_t)N * S);
-    d2h(hout->cost, R.cost, 8 * (size_t)C * S);
-    if (tab) {
-        double* dstd[6] = {hin->tab_s, hin->tab_d, hin->tab_vs, hin->tab_vd, hin->tab_vx, hin->tab_vy};
-        for (int k = 0; k < 6; k++) d2h(dstd[k], tabd + k * (size_t)TS * S, 8 * (size_t)TS * S);
-        d2h(hin->tab_valid, tabi, 4 * (size_t)TS * S); d2h(hin->tab_lane, tabi + (size_t)TS * S, 4 * (size_t)TS * S);
-    }
-    if (!small && (!ok || hipStreamSynchronize(st) != hipSuccess)) return PP_ERR_HIP;
-    return PP_OK;
-}
-
-int32_t pp_plan_reset(pp_map* M, int32_t device) {
-    if (!M || device < 0 || device >= kMaxDev) return PP_ERR_ARG;
-    std::lock_guard<std::mutex> lk(M->dev[device].frame_mu);
-    M->dev[device].plan_table.cars.clear();
-    return PP_OK;
-}
-
-// One telemetry frame (the onMessage replacement): C = 3 (one speed: max_speed), reference mode.
-#ifdef PP_FRAME_PROF
-// diagnostic builds (-DPP_FRAME_PROF): per-frame host and device intervals, summed (us) — host:
-// staging until the launch, the launch call, launch-to-done, done-to-return; device (100 MHz
-// clock): input copy, the frame's body, output copy; and the frame count. pp_frame_prof_read
-// returns and clears them.
-static double g_fprof[8];
-static double fprof_now() {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-int32_t pp_frame_prof_read(double* out8) {
-    for (int i = 0; i < 8; i++) { out8[i] = g_fprof[i]; g_fprof[i] = 0; }
-    return PP_OK;
-}
-#endif
-int32_t pp_plan_frame(pp_map* M, int32_t device, double ego_x, double ego_y, double ego_yaw_deg,
-                      double ego_speed_mph, const double* prev_x, const double* prev_y, int32_t n_prev,
-                      const int32_t* car_id, const double* car_x, const double* car_y,
-                      const double* car_vx, const double* car_vy, int32_t n_cars,
-                      int32_t* target_lane, double* next_x, double* next_y, int32_t* n_out) {
-    if (!M || !target_lane || !next_x || !next_y || !n_out || n_cars < 0 || n_cars > PP_MAX_CARS ||
-        device < 0 || device >= kMaxDev || (n_prev > 0 && (!prev_x || !prev_y)) ||
-        (n_cars > 0 && (!car_id || !car_x || !car_y || !car_vx || !car_vy)))
-        return PP_ERR_ARG;
-    if (*target_lane < 0 || *target_lane >= NL) return PP_ERR_ARG;
-#ifdef PP_FRAME_PROF
-    const double h0 = fprof_now();
-#endif
-    // host staging: one scene, SoA with S = 1 (std::map order: stable sort by id, last row of a
-    // duplicated id wins as in `sensor_fusion_cars[id]` assignment, src/main.cpp:1329)
-    struct Row { int32_t id; double x, y, vx, vy; };
-    std::vector<Row> rows;
-    for (int j = 0; j < n_cars; j++) {
-        bool dup = false;
-        for (auto& r : rows) if (r.id == car_id[j]) { r = {car_id[j], car_x[j], car_y[j], car_vx[j], car_vy[j]}; dup = true; }
-        if (!dup) rows.push_back({car_id[j], car_x[j], car_y[j], car_vx[j], car_vy[j]});
-    }
-    std::stable_sort(rows.begin(), rows.end(), [](const Row& a, const Row& b) { return a.id < b.id; });
-    const int nc = (int)rows.size();
-    // device scratch layout (bytes): doubles then ints, then the scene info (the target lane)
-    constexpr int N = 50;
-    constexpr int TS = PP_MAX_CARS;
-    struct Frame {
-        double ego[4], px[PP_PREV_KEEP], py[PP_PREV_KEEP], cx[PP_MAX_CARS], cy[PP_MAX_CARS],
-            cvx[PP_MAX_CARS], cvy[PP_MAX_CARS];
-        double nx[N], ny[N], cost[NL];
-        double ts[TS], td[TS], tvs[TS], tvd[TS], tvx[TS], tvy[TS];        // the car table's slots
-        int32_t tid[TS], tvalid[TS], tlane[TS];
-        int32_t nprev, ptl, ncars, cid[PP_MAX_CARS], winner, nout;
-        uint32_t status;
-        pp_scene_info info;
-    };
-    DeviceGuard g(device);
-    std::lock_guard<std::mutex> frame_lock(M->dev[device].frame_mu);
-    DevState& DS = M->dev[device];
-    Frame* d = nullptr;
-    constexpr size_t kFlagOff = (sizeof(Frame) + 63) / 64 * 64;
-    {   // per-device scratch, made once: the device frame, its pinned host copy, the frame stream
-        std::lock_guard<std::mutex> lk(M->mu);
-        int rc = dev_init(M, device);
-        if (rc) return rc;
-        // (both copies kFlagOff bytes: the 16-B units of the last fields may pass sizeof(Frame))
-        if (!DS.frame && hipMalloc(&DS.frame, kFlagOff) != hipSuccess) return PP_ERR_NOMEM;
-        if (!DS.frame_host) {
-            if (hipHostMalloc(&DS.frame_host, kFlagOff + 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-                return PP_ERR_NOMEM;
-            memset(DS.frame_host, 0, kFlagOff + 64);
-            DS.frame_seq = 0;
-        }
-        if (!DS.frame_stream && hipStreamCreateWithFlags(&DS.frame_stream, hipStreamNonBlocking) != hipSuccess)
-            return PP_ERR_HIP;
-        d = (Frame*)DS.frame;
-    }
-    Frame& h = *(Frame*)DS.frame_host;
-    volatile uint32_t* flag = (volatile uint32_t*)((char*)DS.frame_host + kFlagOff);
-    // (only the words the frame's ranges carry are written: the previous path's unused tail is
-    // zeroed, every other input range is filled below)
-    memset(h.px, 0, sizeof h.px); memset(h.py, 0, sizeof h.py);
-    const bool poison = dbg(PP_DBG_POISON) != 0;
-    if (poison) {     // the outputs' staging starts NaN-filled (pp_eval poisons them on the device too)
-        memset(h.nx, 0xFF, sizeof h.nx); memset(h.ny, 0xFF, sizeof h.ny); memset(h.cost, 0xFF, sizeof h.cost);
-        memset(&h.winner, 0xFF, sizeof h.winner); memset(&h.nout, 0xFF, sizeof h.nout);
-        memset(&h.status, 0xFF, sizeof h.status); memset(&h.info, 0xFF, sizeof h.info);
-    }
-    h.ego[0] = ego_x; h.ego[1] = ego_y; h.ego[2] = ego_yaw_deg; h.ego[3] = ego_speed_mph;
-    for (int i = 0; i < PP_PREV_KEEP && i < n_prev; i++) { h.px[i] = prev_x[i]; h.py[i] = prev_y[i]; }
-    h.nprev = n_prev; h.ptl = *target_lane; h.ncars = nc;
-    for (int j = 0; j < nc; j++) {
-        h.cid[j] = rows[j].id; h.cx[j] = rows[j].x; h.cy[j] = rows[j].y; h.cvx[j] = rows[j].vx; h.cvy[j] = rows[j].vy;
-    }
-    // the reference's std::map, laid out over the union of its ids and this frame's (any ints)
-    const pptab::Slots hs = {1, h.tid, h.tvalid, h.tlane, h.ts, h.td, h.tvs, h.tvd, h.tvx, h.tvy};
-    const int nu = DS.plan_table.union_size(h.cid, nc);
-    if (nu > TS) return PP_ERR_ARG;                     // more than PP_MAX_CARS distinct cars
-    const int nslots = DS.plan_table.layout(h.cid, nc, hs, 0, nu, poison);
-    if (nslots < 0) return PP_ERR_ARG;
-    hipStream_t st = DS.frame_stream;
-    pp_scene_batch B;
-    memset(&B, 0, sizeof(B));
-    B.n_scenes = 1; B.car_stride = PP_MAX_CARS;
-    B.ego_x = &d->ego[0]; B.ego_y = &d->ego[1]; B.ego_yaw_deg = &d->ego[2]; B.ego_speed_mph = &d->ego[3];
-    B.prev_x = d->px; B.prev_y = d->py; B.n_prev = &d->nprev; B.prev_target_lane = &d->ptl;
-    B.n_cars = &d->ncars; B.car_id = d->cid; B.car_x = d->cx; B.car_y = d->cy; B.car_vx = d->cvx; B.car_vy = d->cvy;
-    B.tab_slots = nslots; B.tab_id = d->tid;
-    B.tab_valid = d->tvalid; B.tab_lane = d->tlane; B.tab_s = d->ts; B.tab_d = d->td;
-    B.tab_vs = d->tvs; B.tab_vd = d->tvd; B.tab_vx = d->tvx; B.tab_vy = d->tvy;
-    pp_params P;
-    pp_params_default(&P);
-    P.n_speeds = 1;
-    pp_result R;
-    memset(&R, 0, sizeof(R));
-    R.winner = &d->winner; R.n_out = &d->nout; R.next_x = d->nx; R.next_y = d->ny; R.cost = d->cost;
-    R.status = &d->status; R.info = &d->info;
-    // The frame's words that carry data: inputs (ego, previous path, this frame's rows, the table's
-    // nslots slots) and outputs (plan, costs, winner / count / status / info, the slots again).
-    FrameIO io;
-    memset(&io, 0, offsetof(FrameIO, inl));
-    // (each field's bytes rounded out to whole 16-B units: the extra words are other fields of the
-    // frame — inputs the kernel overwrites nothing of, outputs the host does not read — and a unit
-    // range touching the previous one joins it)
-    bool fio_full = false;        // a range beyond the kernel argument's kFioMax (never: 15 in, 10 out)
-    auto add = [&](bool in, const void* p, size_t bytes) {
-        if (!bytes) return;
-        const size_t b0 = (size_t)((const char*)p - (const char*)&h);
-        const uint32_t u0 = (uint32_t)(b0 / 16), u1 = (uint32_t)((b0 + bytes + 15) / 16);
-        int& n = in ? io.n_in : io.n_out;
-        uint32_t* off = in ? io.in_off : io.out_off;
-        uint32_t* len = in ? io.in_len : io.out_len;
-        if (n > 0 && u0 <= off[n - 1] + len[n - 1] && u0 >= off[n - 1]) {
-            if (u1 > off[n - 1] + len[n - 1]) len[n - 1] = u1 - off[n - 1];
-            return;
-        }
-        if (n >= kFioMax) { fio_full = true; return; }
-        off[n] = u0; len[n] = u1 - u0;
-        n++;
-    };
-    const size_t ns = (size_t)nslots, ncs = (size_t)nc;
-    add(true, h.ego, sizeof h.ego + sizeof h.px + sizeof h.py);   // ego, px, py: adjacent
-    add(true, h.cx, 8 * ncs); add(true, h.cy, 8 * ncs); add(true, h.cvx, 8 * ncs); add(true, h.cvy, 8 * ncs);
-    add(true, h.ts, 8 * ns); add(true, h.td, 8 * ns); add(true, h.tvs, 8 * ns); add(true, h.tvd, 8 * ns);
-    add(true, h.tvx, 8 * ns); add(true, h.tvy, 8 * ns);
-    add(true, h.tid, 4 * ns); add(true, h.tvalid, 4 * ns); add(true, h.tlane, 4 * ns);
-    add(true, &h.nprev, 4 * (3 + ncs));                          // nprev, ptl, ncars, cid[nc]: adjacent
-    add(false, h.nx, sizeof h.nx + sizeof h.ny + sizeof h.cost);  // nx, ny, cost: adjacent
-    add(false, h.ts, 8 * ns); add(false, h.td, 8 * ns); add(false, h.tvs, 8 * ns); add(false, h.tvd, 8 * ns);
-    add(false, h.tvx, 8 * ns); add(false, h.tvy, 8 * ns);
-    add(false, h.tvalid, 4 * ns); add(false, h.tlane, 4 * ns);
-    add(false, &h.winner, (size_t)((const char*)(&h.info + 1) - (const char*)&h.winner));   // winner .. info
-    static_assert(offsetof(Frame, px) == offsetof(Frame, ego) + sizeof(double) * 4 &&
-                  offsetof(Frame, py) == offsetof(Frame, px) + sizeof(double) * PP_PREV_KEEP &&
-                  offsetof(Frame, ny) == offsetof(Frame, nx) + sizeof(double) * N &&
-                  offsetof(Frame, cost) == offsetof(Frame, ny) + sizeof(double) * N &&
-                  offsetof(Frame, cid) == offsetof(Frame, nprev) + 12 && sizeof(pp_scene_info) % 4 == 0,
-                  "adjacent frame fields");
-    if (fio_full) return PP_ERR_STATE;
-    {   // the input units in range order, inline where they fit
-        int nu = 0;
-        for (int r = 0; r < io.n_in; r++) nu += (int)io.in_len[r];
-        io.n_inl = 0;
-        if (nu <= kFioInline) {
-            const uint4* hu = (const uint4*)&h;
-            for (int r = 0; r < io.n_in; r++)
-                for (uint32_t w = 0; w < io.in_len[r]; w++) io.inl[io.n_inl++] = hu[io.in_off[r] + w];
-        }
-    }
-    void* hdev = nullptr;
-    if (hipHostGetDevicePointer(&hdev, DS.frame_host, 0) != hipSuccess) return PP_ERR_HIP;
-    io.h_in = (const uint4*)hdev; io.h_out = (uint4*)hdev; io.d_frame = (uint4*)d;
-    io.h_flag = (uint32_t*)((char*)hdev + kFlagOff);
-    io.seq = ++DS.frame_seq;
-#ifdef PP_FRAME_PROF
-    const double h1 = fprof_now();
-#endif
-    int rc = eval_impl(M, &B, &P, &R, device, (void*)st, &io);
-#ifdef PP_FRAME_PROF
-    const double h2 = fprof_now();
-#endif
-    if (rc == PP_OK) {
-        // the kernel's done word; the stream is polled now and then, so a failed launch or a fault
-        // ends the wait with an error
-        for (uint64_t spin = 1; *flag != io.seq; spin++) {
-            if ((spin & 1023) == 0) {
-                const hipError_t e = hipStreamQuery(st);
-                if (e == hipSuccess && *flag != io.seq) { rc = PP_ERR_HIP; break; }
-                if (e != hipSuccess && e != hipErrorNotReady) { rc = PP_ERR_HIP; break; }
-            }
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#endif
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-#ifdef PP_FRAME_PROF
-        const double h3 = fprof_now();
-        const volatile uint32_t* fw = flag;
-        g_fprof[0] += h1 - h0; g_fprof[1] += h2 - h1; g_fprof[2] += h3 - h2;
-        g_fprof[4] += (uint32_t)(fw[5] - fw[4]) / 100.0; g_fprof[5] += (uint32_t)(fw[6] - fw[5]) / 100.0;
-        g_fprof[6] += (uint32_t)(fw[7] - fw[6]) / 100.0; g_fprof[7] += 1;
-        g_fprof[3] -= h3;             // (done-to-return: the return adds its time)
-#endif
-    } else if (rc == PP_ERR_STATE) {
-        // a launch shape other than the one-launch step (debug shapes, maps beyond the LDS): copies
-        if (hipMemcpyAsync(d, &h, sizeof(Frame), hipMemcpyHostToDevice, st) != hipSuccess) return PP_ERR_HIP;
-        rc = eval_impl(M, &B, &P, &R, device, (void*)st, nullptr);
-        if (rc == PP_OK && (hipMemcpyAsync(&h, d, sizeof(Frame), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                            hipStreamSynchronize(st) != hipSuccess))
-            rc = PP_ERR_HIP;
-    }
-    if (rc != PP_OK) return rc;
-    DS.plan_table.take_back(hs, 0, nslots);
-    *n_out = h.nout;
-    for (int i = 0; i < h.nout && i < N; i++) { next_x[i] = h.nx[i]; next_y[i] = h.ny[i]; }
-    *target_lane = h.info.target_lane;
-#ifdef PP_FRAME_PROF
-    g_fprof[3] += fprof_now();
-#endif
-    return PP_OK;
-}
-
-}  // extern "C"
+#include "pp_host_map.h"     // pp_map, DevState, StreamWS, build_map, dev_init
+#include "pp_launch.h"       // workspace, launch-shape choices, eval_impl and its launch sequences
+#include "pp_api.h"          // C ABI: params, maps, reserve, pp_eval, debug, timing, synthesis, diagnostics
+#include "pp_api_rollout.h"  // C ABI: rollouts, judge, follow
+#include "pp_api_frame.h"    // C ABI: pp_plan_batch_host, pp_plan_reset, pp_plan_frame

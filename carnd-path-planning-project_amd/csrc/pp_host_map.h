@@ -1,0 +1,430 @@
+// pp_host_map.h — host: pp_map, per-device state, per-stream workspace, the map tables and their
+// upload. Part of pp_eval.hip's translation unit.
+#pragma once
+
+// ================================================================================================
+// host side: map, per-device state, C-ABI
+// ================================================================================================
+namespace {
+
+constexpr int kMaxDev = 16;
+constexpr int kMaxWaypoints = 1 << 24;
+constexpr int kPrepD = 12 + 4 * NL;   // doubles per scene in PrepV (see prep_bind)
+constexpr int kPrepI = 7;
+
+// pp_eval's device workspaces, one set per HIP stream: evaluations on different streams never
+// share intermediate buffers, and evaluations on one stream are ordered by it. A buffer is grown
+// only after that stream has drained (it is the only stream using it).
+// the split of shard-sized batches: parts (streams) per call, at most kSplitMax (split_parts)
+constexpr int kSplitMax = 4;
+// parts per call: a batch beyond kSplitMaxScenes runs as chunks of parts, part t on stream t % streams
+// (split_chunks); each part has its own flagged-group count word and 4 timing-event slots
+constexpr int kPartMax = 16;
+struct StreamWS {
+    void* ws = nullptr;           // prep workspace (per evaluation: scene x draw)
+    int64_t ws_cap = 0;
+    void* rec = nullptr;          // reference-mode winner record (per scene)
+    int64_t rec_cap = 0;
+    uint32_t* gbits = nullptr;    // k_cand groups holding a kLimSlow scene (bitmap; all zero between calls)
+    int64_t gbits_cap = 0;        // words
+    void* srt = nullptr;          // k_sort_cars' visit-major rows (SortedCars)
+    size_t srt_cap = 0;           // bytes
+    hipStream_t st2[kSplitMax - 1] = {};   // the split's other streams (shard-sized batches)
+    hipEvent_t fork = nullptr, join[kSplitMax - 1] = {};
+};
+struct DevState {
+    bool init = false;
+    double* map = nullptr;        // kMapArrays * n
+    uint2* wgrid = nullptr;       // the closest-waypoint cell table (pp_map::wgrid)
+    double2* wseg = nullptr;      // reference segment lengths and reciprocals (pp_map::wseg)
+    double* atab = nullptr;       // the approach table (pp_map::atab)
+    double* lanetab = nullptr;    // synth tables: lc_x[NL n] lc_y[NL n] seg_len[NL n] tan_x[NL n] tan_y[NL n]
+    double* arctab = nullptr;     // pp_map::arctab, uploaded on the first follow call (arc_init)
+    std::map<void*, StreamWS> sws;  // per hip_stream
+    void* frame = nullptr;        // single-frame scratch (pp_plan_frame)
+    void* frame_host = nullptr;   // its pinned host staging copy (coherent: k_plan_frame reads and
+                                  // writes it; the frame's done word follows the frame)
+    hipStream_t frame_stream = nullptr;  // pp_plan_frame's stream
+    uint32_t frame_seq = 0;       // the last frame's done word
+    std::mutex frame_mu;          // one pp_plan_frame at a time per device (frame scratch + car table)
+    void* stage = nullptr;        // pp_plan_batch_host staging buffer
+    size_t stage_cap = 0;
+    void* stage_host = nullptr;   // its pinned host mirror (one copy per direction and region)
+    std::mutex stage_mu;          // one pp_plan_batch_host at a time per device
+    pptab::CarTable plan_table;   // pp_plan_frame's persistent car table (the reference's std::map)
+    int timing = 0;               // pp_timing_enable: 0 off, 1 every kernel, 2 K2 only
+    std::vector<hipEvent_t> ev_pool;
+    // groups of 4 kPartMax per pp_eval: before K1, after K1, after K2, after K3/K4 on the launch
+    // stream (the split: those four per part, each part's on its own stream, events 4 h .. 4 h + 3)
+    std::vector<hipEvent_t> ev_rec;
+    // per group: bit 0 K3/K4 launched, bits 1-3 the split's parts (0: none), bit 4 K2's events only,
+    // bit 5 no K1 kernel (the one-launch step)
+    std::vector<int> ev_kind;
+};
+
+}  // namespace
+
+struct pp_map {
+    int n = 0;
+    std::vector<double> geom;     // kMapArrays * n (MapG layout)
+    std::vector<double> ptab;     // (4 + 2 NL) * n: ref xy, normal, lane centres (pp_map_geometry)
+    std::vector<double> lanetab;  // 5 NL * n
+    std::vector<double> arctab;   // reactive traffic's arc prefix (ppfollow::build_arc): cum[NL n] loop[NL]
+    int fastm = 0;                // MapV::fastm: bit 1: every lane segment's rdenom in [2^-500, 2^500]; bit 2: approach_seg's map bounds
+    std::vector<uint2> wgrid;     // closest-waypoint cell table (build_wgrid; empty: none)
+    std::vector<double2> wseg;    // reference segment lengths and reciprocals (build_wseg; empty: none)
+    std::vector<double> atab;     // lane matching's approach table (build_atab; empty: none)
+    WGrid wg;                     // its geometry (cells: the device copy, set per device)
+    DevState dev[kMaxDev];
+    std::mutex mu;
+};
+
+namespace {
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int d) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(d); }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// reactive traffic's arc prefix from the host lanetab's seg_len (for a pp_map_create_device map: the
+// mirrored device values), one left-to-right sum per lane
+void fill_arctab(pp_map* M) {
+    M->arctab.assign(ppfollow::arc_doubles(M->n), 0.0);
+    ppfollow::build_arc(M->lanetab.data() + 2 * NL * (size_t)M->n, M->n, M->arctab.data());
+}
+
+// pp_map_geometry's table from the MapG layout: per waypoint ref xy, normal, lane centres
+void fill_ptab(pp_map* M) {
+    const int n = M->n;
+    const double* g = M->geom.data();
+    M->ptab.assign((4 + 2 * NL) * (size_t)n, 0.0);
+    for (int i = 0; i < n; i++) {
+        double* o = &M->ptab[(4 + 2 * NL) * (size_t)i];
+        o[0] = g[i]; o[1] = g[n + i]; o[2] = g[2 * n + i]; o[3] = g[3 * n + i];
+        for (int r = 0; r < NL; r++) { o[4 + 2 * r] = g[(4 + r) * n + i]; o[5 + 2 * r] = g[(4 + NL + r) * n + i]; }
+    }
+    M->fastm = 1;
+    for (size_t i = (size_t)(4 + 3 * NL) * n; i < (size_t)(4 + 4 * NL) * n; i++)
+        if (!(g[i] >= 0x1p-500 && g[i] <= 0x1p500)) M->fastm = 0;
+    // bit 2 (lane matching's approach runs, pp_device.h approach_seg): every lane segment's rdenom
+    // >= 1 m^2 and every lane centre within 4e4 m of the origin
+    bool appr = M->fastm != 0;
+    for (size_t i = (size_t)(4 + 3 * NL) * n; i < (size_t)(4 + 4 * NL) * n; i++) appr = appr && g[i] >= 1.0;
+    for (size_t i = (size_t)4 * n; i < (size_t)(4 + 2 * NL) * n; i++) appr = appr && std::fabs(g[i]) < 4e4;
+    if (appr) M->fastm |= 2;
+}
+
+// The closest-waypoint cell table (pp_device.h WGrid, init_reference_waypoint). Cells of 16 m
+// within 32 m of the waypoint polyline get a list: waypoint w can be the closest one to a point of
+// cell B only if its distance to B, dmin(w, B), is at most U = min over all waypoints of the
+// largest distance from w' to B (the closest waypoint of any point of B is at most U away). B is
+// grown by 0.5 m on each side (the kernel's cell index rounds), and the test carries a relative
+// margin of 1e-6 (the kernel's squared distances round by a few ulps): the list holds every
+// waypoint that can be the scan's answer. Lists of up to 4 (the highway map's cells near the road
+// hold 1-4); a cell with more, or away from the road, has none (0xFFFFFFFF: the kernel scans).
+// Maps of more than 65,535 waypoints, or whose table would take more than 5e7 distance tests to
+// build, get no table.
+constexpr double kWgridMaxCells = 4e6;
+void build_wgrid(pp_map* M) {
+    constexpr double kCell = 16.0, kNear = 32.0, kGrow = 0.5;
+    const int n = M->n;
+    M->wgrid.clear();
+    M->wg = WGrid{};
+    if (n < 1 || n > 65535) return;
+    const double* rx = M->geom.data();
+    const double* ry = rx + n;
+    double x0 = rx[0], x1 = rx[0], y0 = ry[0], y1 = ry[0];
+    for (int i = 0; i < n; i++) {
+        if (!std::isfinite(rx[i]) || !std::isfinite(ry[i])) return;
+        x0 = std::min(x0, rx[i]); x1 = std::max(x1, rx[i]); y0 = std::min(y0, ry[i]); y1 = std::max(y1, ry[i]);
+    }
+    const double gx0 = x0 - 2 * kNear, gy0 = y0 - 2 * kNear;
+    const double wdt = x1 - x0 + 4 * kNear, hgt = y1 - y0 + 4 * kNear;
+    if (!(wdt / kCell < 1e5 && hgt / kCell < 1e5)) return;
+    const int gnx = (int)std::ceil(wdt / kCell), gny = (int)std::ceil(hgt / kCell);
+    // at most 4e6 cells (a 32 km square; 32 MB on the host and the device): a map spread wider
+    // keeps the full scan (two waypoints 1,000 km apart would ask for ~4e9 cells)
+    if ((double)gnx * (double)gny > kWgridMaxCells) return;
+    // cells near the polyline: sample every segment every 2 m, mark cells within kNear
+    std::vector<uint8_t> near((size_t)gnx * gny, 0);
+    const int R = (int)std::ceil(kNear / kCell);
+    for (int i = 0; i < n; i++) {
+        const int j = (i + 1) % n;
+        const double len = std::hypot(rx[j] - rx[i], ry[j] - ry[i]);
+        const int ns = std::max(1, (int)std::ceil(len / 2.0));
+        for (int k = 0; k <= ns; k++) {
+            const double t = (double)k / ns;
+            const double px = rx[i] + (rx[j] - rx[i]) * t, py = ry[i] + (ry[j] - ry[i]) * t;
+            const int ci = (int)((px - gx0) / kCell), cj = (int)((py - gy0) / kCell);
+            for (int dj = -R; dj <= R; dj++)
+                for (int di = -R; di <= R; di++) {
+                    const int a = ci + di, b = cj + dj;
+                    if (a >= 0 && b >= 0 && a < gnx && b < gny) near[(size_t)b * gnx + a] = 1;
+                }
+        }
+    }
+    size_t nnear = 0;
+    for (uint8_t v : near) nnear += v;
+    if ((double)nnear * n > 5e7) return;
+    std::vector<uint2> cells((size_t)gnx * gny, uint2{0xFFFFFFFFu, 0xFFFFFFFFu});
+    std::vector<int> cand;
+    for (int cj = 0; cj < gny; cj++)
+        for (int ci = 0; ci < gnx; ci++) {
+            if (!near[(size_t)cj * gnx + ci]) continue;
+            const double bx0 = gx0 + ci * kCell - kGrow, bx1 = gx0 + (ci + 1) * kCell + kGrow;
+            const double by0 = gy0 + cj * kCell - kGrow, by1 = gy0 + (cj + 1) * kCell + kGrow;
+            double U = INFINITY;
+            for (int i = 0; i < n; i++) {
+                const double fx = std::max(std::fabs(rx[i] - bx0), std::fabs(rx[i] - bx1));
+                const double fy = std::max(std::fabs(ry[i] - by0), std::fabs(ry[i] - by1));
+                U = std::min(U, fx * fx + fy * fy);
+            }
+            const double lim = U * (1 + 1e-6) + 1e-6;
+            cand.clear();
+            for (int i = 0; i < n && cand.size() <= 4; i++) {
+                const double dx = std::max({bx0 - rx[i], rx[i] - bx1, 0.0});
+                const double dy = std::max({by0 - ry[i], ry[i] - by1, 0.0});
+                if (dx * dx + dy * dy <= lim) cand.push_back(i);
+            }
+            if (cand.empty() || cand.size() > 4) continue;
+            while (cand.size() < 4) cand.push_back(cand.back());
+            cells[(size_t)cj * gnx + ci] = uint2{(uint32_t)cand[0] | ((uint32_t)cand[1] << 16),
+                                                 (uint32_t)cand[2] | ((uint32_t)cand[3] << 16)};
+        }
+    M->wgrid.swap(cells);
+    M->wg.gx0 = gx0; M->wg.gy0 = gy0; M->wg.ginv = 1.0 / kCell; M->wg.gnx = gnx; M->wg.gny = gny;
+}
+
+// Map::project_speed's segment length (src/main.cpp:332-339: w = ref_b - ref_{b-1}, |w| =
+// sqrt(wx^2 + wy^2), the same operations as the kernel, unfused, correctly rounded sqrt) and
+// RN(1 / |w|) by IEEE division, per segment b (project_speed then divides by the reciprocal with one
+// Markstein correction: the correctly rounded quotient, ppd::div_by_rcp). Only for maps whose
+// lengths all lie in [2^-500, 2^500] (div_by_rcp's divisor range); else none.
+void build_wseg(pp_map* M) {
+    const int n = M->n;
+    M->wseg.clear();
+    const double* rx = M->geom.data();
+    const double* ry = rx + n;
+    std::vector<double2> t(n);
+    for (int b = 0; b < n; b++) {
+        const int a = (int)(((int64_t)b - 1 + n) % n);
+        const double wx = rx[b] - rx[a], wy = ry[b] - ry[a];
+        const double wvl = std::sqrt(wx * wx + wy * wy);
+        if (!(wvl >= 0x1p-500 && wvl <= 0x1p500)) return;
+        t[b] = double2{wvl, 1.0 / wvl};
+    }
+    M->wseg.swap(t);
+}
+
+// Lane matching's approach table (pp_device.h approach_cert): per lane segment b (waypoint b - 1 to
+// b) and lane l, d = RN(pb - pa) (the walk's own differences), c = pa.d, and the certain test's
+// constants c + rdenom + kAtabMargin (forward) and c - 1 - kAtabMargin (backward), rdenom the map's
+// own table value. Only for maps with fastm bit 2 (the bounds its margin argument needs).
+void build_atab(pp_map* M) {
+    M->atab.clear();
+    if (!(M->fastm & 2)) return;
+    const int n = M->n;
+    const double* g = M->geom.data();
+    const double* lcx = g + 4 * (size_t)n;
+    const double* lcy = g + (4 + NL) * (size_t)n;
+    const double* llen = g + (4 + 2 * NL) * (size_t)n;
+    const double* lden = g + (4 + 3 * NL) * (size_t)n;
+    std::vector<double> t((size_t)kAtabD * n, 0.0);
+    for (int b = 0; b < n; b++) {
+        const int a = b == 0 ? n - 1 : b - 1;
+        double* r = &t[(size_t)kAtabD * b];
+        for (int l = 0; l < NL; l++) {
+            const double pax = lcx[(size_t)l * n + a], pay = lcy[(size_t)l * n + a];
+            const double dx = lcx[(size_t)l * n + b] - pax, dy = lcy[(size_t)l * n + b] - pay;
+            const double c = pax * dx + pay * dy;
+            r[2 * l] = dx;
+            r[2 * l + 1] = dy;
+            r[2 * NL + l] = c + lden[(size_t)l * n + b] + kAtabMargin;
+            r[3 * NL + l] = c - 1.0 - kAtabMargin;
+            r[4 * NL + l] = llen[(size_t)l * n + b];
+        }
+    }
+    M->atab.swap(t);
+}
+
+// The optional per-map tables (cell table, segment reciprocals, approach table) speed K1 up and
+// never change a result: a map whose tables cannot be built (an allocation failure included) runs
+// without them. Nothing here throws across the C-ABI.
+void build_tables(pp_map* M) {
+    try { build_wgrid(M); } catch (...) { M->wgrid.clear(); M->wgrid.shrink_to_fit(); M->wg = WGrid{}; }
+    try { build_wseg(M); } catch (...) { M->wseg.clear(); M->wseg.shrink_to_fit(); }
+    try { build_atab(M); } catch (...) { M->atab.clear(); M->atab.shrink_to_fit(); }
+}
+
+void free_map_tables(DevState& D) {
+    if (D.wgrid) (void)hipFree(D.wgrid);
+    if (D.wseg) (void)hipFree(D.wseg);
+    if (D.atab) (void)hipFree(D.atab);
+    D.wgrid = nullptr; D.wseg = nullptr; D.atab = nullptr;
+}
+
+// the device copies of the cell table, the segment table and the approach table (dev_init,
+// pp_map_create_device)
+int upload_wgrid(pp_map* M, DevState& D) {
+    if (!M->wgrid.empty()) {
+        if (hipMalloc(&D.wgrid, sizeof(uint2) * M->wgrid.size()) != hipSuccess) return PP_ERR_NOMEM;
+        if (hipMemcpy(D.wgrid, M->wgrid.data(), sizeof(uint2) * M->wgrid.size(), hipMemcpyHostToDevice) != hipSuccess)
+            return PP_ERR_HIP;
+    }
+    if (!M->wseg.empty()) {
+        if (hipMalloc(&D.wseg, sizeof(double2) * M->wseg.size()) != hipSuccess) return PP_ERR_NOMEM;
+        if (hipMemcpy(D.wseg, M->wseg.data(), sizeof(double2) * M->wseg.size(), hipMemcpyHostToDevice) != hipSuccess)
+            return PP_ERR_HIP;
+    }
+    if (!M->atab.empty()) {
+        if (hipMalloc(&D.atab, sizeof(double) * M->atab.size()) != hipSuccess) return PP_ERR_NOMEM;
+        if (hipMemcpy(D.atab, M->atab.data(), sizeof(double) * M->atab.size(), hipMemcpyHostToDevice) != hipSuccess)
+            return PP_ERR_HIP;
+    }
+    return PP_OK;
+}
+
+// Map::Init (src/main.cpp:89-131) + derived tables, on the host (done once per map).
+int build_map(pp_map* M, const double* wx, const double* wy, int n) {
+    M->n = n;
+    std::vector<double> nx(n), ny(n), lcx(NL * n), lcy(NL * n);
+    auto W = [n](int i) { return (int)(((int64_t)i + n) % n); };
+    for (int i = 0; i < n; i++) {
+        const int p = W(i - 1);
+        const double dx = wx[i] - wx[p], dy = wy[i] - wy[p];
+        const double len = std::sqrt(dx * dx + dy * dy);
+        if (!(len > 0)) return PP_ERR_ARG;    // duplicate consecutive waypoints: Map::Init divides by 0
+        nx[i] = dy / len;
+        ny[i] = -dx / len;
+    }
+    for (int i = 0; i < n; i++) {
+        const int q = W(i + 1);
+        double ax = (nx[i] + nx[q]) / 2, ay = (ny[i] + ny[q]) / 2;
+        const double a_n = std::atan2(ny[i], nx[i]);
+        const double a_avg = std::atan2(ay, ax);
+        const double cos_alpha = std::cos(a_avg - a_n);
+        ax /= cos_alpha;
+        ay /= cos_alpha;
+        for (int r = 0; r < NL; r++) {
+            const double off = 4.0 * (r + 0.5);
+            lcx[r * n + i] = wx[i] + ax * off;
+            lcy[r * n + i] = wy[i] + ay * off;
+        }
+    }
+    M->geom.assign(kMapArrays * (size_t)n, 0.0);
+    double* g = M->geom.data();
+    for (int i = 0; i < n; i++) {
+        g[i] = wx[i]; g[n + i] = wy[i]; g[2 * n + i] = nx[i]; g[3 * n + i] = ny[i];
+        for (int r = 0; r < NL; r++) {
+            g[(4 + r) * n + i] = lcx[r * n + i];
+            g[(4 + NL + r) * n + i] = lcy[r * n + i];
+            const int p = W(i - 1);
+            const double dx = lcx[r * n + i] - lcx[r * n + p], dy = lcy[r * n + i] - lcy[r * n + p];
+            g[(4 + 2 * NL + r) * n + i] = std::sqrt(dx * dx + dy * dy);    // Map::get_lane_length
+            const double ex = lcx[r * n + p] - lcx[r * n + i], ey = lcy[r * n + p] - lcy[r * n + i];
+            const double den = ex * ex + ey * ey;                           // helpers.h:202 rdenom
+            g[(4 + 3 * NL + r) * n + i] = den;
+            g[(4 + 4 * NL + r) * n + i] = 1.0 / den;
+        }
+    }
+    fill_ptab(M);
+    build_tables(M);
+    M->lanetab.assign(5 * NL * (size_t)n, 0.0);
+    double* t = M->lanetab.data();
+    for (int r = 0; r < NL; r++)
+        for (int i = 0; i < n; i++) {
+            const double len = g[(4 + 2 * NL + r) * n + i];
+            const int p = W(i - 1);
+            t[0 * NL * n + r * n + i] = lcx[r * n + i];
+            t[1 * NL * n + r * n + i] = lcy[r * n + i];
+            t[2 * NL * n + r * n + i] = len;
+            t[3 * NL * n + r * n + i] = (lcx[r * n + i] - lcx[r * n + p]) / len;
+            t[4 * NL * n + r * n + i] = (lcy[r * n + i] - lcy[r * n + p]) / len;
+        }
+    fill_arctab(M);
+    return PP_OK;
+}
+
+ppsynth::OutBatch out_batch(const pp_scene_batch* b) {
+    ppsynth::OutBatch o;
+    o.S = b->n_scenes;
+    o.ego_x = (double*)b->ego_x; o.ego_y = (double*)b->ego_y;
+    o.ego_yaw_deg = (double*)b->ego_yaw_deg; o.ego_speed_mph = (double*)b->ego_speed_mph;
+    o.prev_x = (double*)b->prev_x; o.prev_y = (double*)b->prev_y;
+    o.n_prev = (int32_t*)b->n_prev; o.prev_target_lane = (int32_t*)b->prev_target_lane;
+    o.n_cars = (int32_t*)b->n_cars; o.car_id = (int32_t*)b->car_id;
+    o.car_x = (double*)b->car_x; o.car_y = (double*)b->car_y;
+    o.car_vx = (double*)b->car_vx; o.car_vy = (double*)b->car_vy;
+    return o;
+}
+
+bool traffic_ok(const pp_traffic* t, const pp_scene_batch* b) {
+    return t && b && t->n_cars >= 0 && t->n_cars <= PP_MAX_CARS && t->lane && t->seg && t->t &&
+           t->offset && t->speed;
+}
+
+bool judge_ok(const pp_judge_cfg* c, const pp_judge* j) {
+    return c && j && ppjudge::cfg_ok(*c) && j->steps && j->flags && j->count && j->first_step &&
+           j->first_car && j->seg_hint && j->off_run && j->head_x && j->head_y && j->ring_vx && j->ring_vy &&
+           j->dist && j->clean_dist && j->min_sep && j->max_speed_mph && j->max_acc && j->max_jerk;
+}
+
+// what the judge reads of a frame: the ego pose, the traffic, the plan
+bool judge_frame_ok(const pp_scene_batch* tel, const pp_traffic* traffic, const pp_result* plan, int32_t consume) {
+    return tel && plan && tel->n_scenes >= 0 && tel->ego_x && tel->ego_y && tel->ego_yaw_deg &&
+           traffic_ok(traffic, tel) && plan->n_out && plan->next_x && plan->next_y && consume >= 1;
+}
+
+bool follow_ok(const pp_follow_cfg* c, const pp_follow* f) {
+    return c && f && ppfollow::cfg_ok(*c) && f->started && f->ego_seg && f->desired && f->next_speed &&
+           f->leader && f->gap;
+}
+
+// what the follow update reads of a frame: the ego's position and speed, the traffic
+bool follow_frame_ok(const pp_scene_batch* tel, const pp_traffic* traffic, int32_t consume) {
+    return tel && tel->n_scenes >= 0 && tel->ego_x && tel->ego_y && tel->ego_speed_mph &&
+           traffic_ok(traffic, tel) && consume >= 1;
+}
+
+ppsynth::TrafficV traffic_view(const pp_traffic* t, int64_t S) {
+    ppsynth::TrafficV v;
+    v.S = S; v.n = t->n_cars; v.lane = t->lane; v.seg = t->seg; v.t = t->t; v.off = t->offset; v.v = t->speed;
+    return v;
+}
+
+ppsynth::LaneTables lane_tables(const double* t, int n) {
+    ppsynth::LaneTables T;
+    T.n = n; T.lc_x = t; T.lc_y = t + NL * n; T.seg_len = t + 2 * NL * n; T.tan_x = t + 3 * NL * n;
+    T.tan_y = t + 4 * NL * n;
+    return T;
+}
+
+int dev_init(pp_map* M, int device) {
+    DevState& D = M->dev[device];
+    if (D.init) return PP_OK;
+    if (hipMalloc(&D.map, sizeof(double) * M->geom.size()) != hipSuccess) return PP_ERR_NOMEM;
+    if (hipMalloc(&D.lanetab, sizeof(double) * M->lanetab.size()) != hipSuccess) return PP_ERR_NOMEM;
+    if (hipMemcpy(D.map, M->geom.data(), sizeof(double) * M->geom.size(), hipMemcpyHostToDevice) != hipSuccess) return PP_ERR_HIP;
+    if (hipMemcpy(D.lanetab, M->lanetab.data(), sizeof(double) * M->lanetab.size(), hipMemcpyHostToDevice) != hipSuccess) return PP_ERR_HIP;
+    const int rc = upload_wgrid(M, D);
+    if (rc != PP_OK) return rc;
+    D.init = true;
+    return PP_OK;
+}
+
+// the device copy of the arc prefix, made on the first follow call on this device (after dev_init,
+// under M->mu)
+int arc_init(pp_map* M, int device) {
+    DevState& D = M->dev[device];
+    if (D.arctab) return PP_OK;
+    if (hipMalloc(&D.arctab, sizeof(double) * M->arctab.size()) != hipSuccess) return PP_ERR_NOMEM;
+    if (hipMemcpy(D.arctab, M->arctab.data(), sizeof(double) * M->arctab.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(D.arctab);
+        D.arctab = nullptr;
+        return PP_ERR_HIP;
+    }
+    return PP_OK;
+}
+
+}  // namespace

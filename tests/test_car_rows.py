@@ -393,7 +393,7 @@ def test_row_counts_every_k1_vs_oracle(env, J):
 @pytest.mark.parametrize("J", [5, 16, 17])
 @pytest.mark.parametrize("D", [15, 16])
 def test_row_counts_draw_boundary(env, J, D):
-    """The one-lane K1 sorts a scene's rows below PP_SORT_DMAX = 16 draws and keeps the identity
+    """The one-lane K1 sorts a scene's rows below kSortDmax = 16 draws and keeps the identity
     order from 16 on; batches this small would otherwise take the grouped K1. The Monte-Carlo
     contract of test_montecarlo.TestMonteCarloGPU.check (costs and draw-averaged costs within 1e-9,
     decisions, output counts and flags exact, the nominal trajectory within TOL), taken through

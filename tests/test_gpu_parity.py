@@ -158,7 +158,7 @@ def test_speed_range_edges_vs_oracle(env, emit):
 
 @pytest.mark.parametrize("n_speeds", [4, 6, 7, 8])
 def test_flat_groups_vs_oracle(env, n_speeds):
-    """All-paths mode in the flat k_cand geometry (round 5, pp_eval.hip cand_geom / cand_group:
+    """All-paths mode in the flat k_cand geometry (round 5, pp_launch.h cand_geom / pp_eval.hip cand_group:
     groups of 256 consecutive candidates, scenes straddling two groups, their spline slots built in
     both and their status flags merged with atomics): C = 18, 21, 24 straddle; C = 12 keeps whole
     scenes per group. A third of the scenes carry speed-edge telemetry, so k_prep routes them to

@@ -1,4 +1,4 @@
-"""The closest-waypoint cell table (round 5; csrc/pp_eval.hip build_wgrid, csrc/pp_device.h
+"""The closest-waypoint cell table (round 5; csrc/pp_host_map.h build_wgrid, csrc/pp_device.h
 init_reference_waypoint): near the road k_prep reads the (at most 4) waypoints that can be the
 closest one to any point of a 16 m cell instead of scanning all of them (Map::init_reference_waypoint,
 src/main.cpp:150-154). The claim is bit-identity with the full scan — the first waypoint with the
