@@ -19,6 +19,32 @@ void launch_follow(const ppsynth::LaneTables& T, const ppfollow::ArcTables& AT, 
                        tel->ego_y, tel->ego_speed_mph, tv, consume, *fc, *fs);
 }
 
+// every argument check of pp_synth_episode and its host twin (no HIP call); *gap: the gap rule in force
+bool episode_ok(const pp_map* M, int64_t first_scene, const pp_episode_cfg* cfg, const pp_follow_cfg* gap_rule,
+                const pp_scene_batch* tel, const pp_traffic* traffic, const pp_judge* js, const pp_follow* fs,
+                pp_follow_cfg* gap) {
+    if (!M || !cfg || !tel || !traffic || first_scene < 0 || tel->n_scenes < 0) return false;
+    if (!tel->ego_x || !tel->ego_y || !tel->ego_yaw_deg || !tel->ego_speed_mph || !tel->prev_x || !tel->prev_y ||
+        !tel->n_prev || !tel->prev_target_lane || !tel->n_cars || !tel->car_id || !tel->car_x || !tel->car_y ||
+        !tel->car_vx || !tel->car_vy)
+        return false;
+    if (!traffic->lane || !traffic->seg || !traffic->t || !traffic->offset || !traffic->speed) return false;
+    if (js && (!js->steps || !js->flags || !js->count || !js->first_step || !js->first_car || !js->seg_hint ||
+               !js->off_run || !js->head_x || !js->head_y || !js->ring_vx || !js->ring_vy || !js->dist ||
+               !js->clean_dist || !js->min_sep || !js->max_speed_mph || !js->max_acc || !js->max_jerk))
+        return false;
+    if (fs && (!fs->started || !fs->ego_seg || !fs->desired || !fs->next_speed || !fs->leader || !fs->gap)) return false;
+    if (!ppepisode::cfg_ok(*cfg) || cfg->n_cars > tel->car_stride) return false;
+    if (tel->tab_valid && (tel->tab_slots < cfg->n_cars || tel->tab_slots > PP_MAX_CARS)) return false;
+    if (gap_rule) *gap = *gap_rule; else pp_follow_cfg_default(gap);
+    // (the follow update takes any headway and standstill gap; a placement by them needs numbers >= 0)
+    if (!ppfollow::cfg_ok(*gap) || !(gap->time_headway >= 0) || !(gap->min_gap >= 0)) return false;
+    const ppfollow::ArcTables A = ppfollow::arc_tables(M->arctab.data(), M->n);
+    double min_loop = A.loop[0];
+    for (int l = 1; l < PP_NUM_LANES; l++) min_loop = A.loop[l] < min_loop ? A.loop[l] : min_loop;
+    return ppepisode::ring_ok(*cfg, *gap, min_loop);
+}
+
 // pp_rollout's loop; with follow state (fc, fs non-null) k_follow runs after pp_eval, with a judge (jc,
 // js non-null) k_judge runs before k_sim
 int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
@@ -179,6 +205,71 @@ int32_t pp_traffic_follow(pp_map* M, const pp_scene_batch* tel, pp_traffic* traf
     }
     launch_follow(T, AT, tel, traffic_view(traffic, tel->n_scenes), consume, cfg, state, (hipStream_t)hip_stream);
     if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
+    return PP_OK;
+}
+
+void pp_episode_cfg_default(pp_episode_cfg* c) {
+    if (!c) return;
+    memset(c, 0, sizeof(*c));
+    c->n_cars = 12;
+    c->ego_speed_min = 0;
+    c->ego_speed_max = 20;
+    c->car_speed_min = 5;
+    c->car_speed_max = 25;
+    c->ahead_share = 0.75;
+    c->extra_gap = 40;
+    c->offset_jitter = 0.3;
+    c->gap_slack = 1e-6;
+}
+
+int32_t pp_synth_episode(pp_map* M, uint64_t seed, int64_t first_scene, const pp_episode_cfg* cfg,
+                         const pp_follow_cfg* gap_rule, pp_scene_batch* tel, pp_traffic* traffic, pp_judge* jstate,
+                         pp_follow* fstate, int32_t device, void* hip_stream) {
+    pp_follow_cfg gap;
+    if (device < 0 || device >= kMaxDev || !episode_ok(M, first_scene, cfg, gap_rule, tel, traffic, jstate, fstate, &gap))
+        return PP_ERR_ARG;
+    traffic->n_cars = cfg->n_cars;
+    if (tel->n_scenes == 0) return PP_OK;
+    DeviceGuard g(device);
+    ppsynth::LaneTables T;
+    {
+        std::lock_guard<std::mutex> lk(M->mu);
+        const int rc = dev_init(M, device);
+        if (rc) return rc;
+        T = lane_tables(M->dev[device].lanetab, M->n);
+    }
+    const ppsynth::OutBatch o = out_batch(tel);
+    pp_judge js;
+    pp_follow fs;
+    memset(&js, 0, sizeof(js));
+    memset(&fs, 0, sizeof(fs));
+    if (jstate) js = *jstate;
+    if (fstate) fs = *fstate;
+    hipLaunchKernelGGL(k_synth_episode, dim3((unsigned)((o.S + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, T,
+                       seed, first_scene, *cfg, gap, o, tel->tab_valid, tel->tab_id, (int)tel->tab_slots,
+                       traffic_view(traffic, o.S), js, jstate ? 1 : 0, fs, fstate ? 1 : 0);
+    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
+    return PP_OK;
+}
+
+int32_t pp_synth_episode_host(const pp_map* M, uint64_t seed, int64_t first_scene, const pp_episode_cfg* cfg,
+                              const pp_follow_cfg* gap_rule, pp_scene_batch* tel, pp_traffic* traffic,
+                              pp_judge* jstate, pp_follow* fstate) {
+    pp_follow_cfg gap;
+    if (!episode_ok(M, first_scene, cfg, gap_rule, tel, traffic, jstate, fstate, &gap)) return PP_ERR_ARG;
+    traffic->n_cars = cfg->n_cars;
+    const ppsynth::LaneTables T = lane_tables(M->lanetab.data(), M->n);
+    const ppsynth::OutBatch o = out_batch(tel);
+    const ppsynth::TrafficV tv = traffic_view(traffic, o.S);
+    pp_judge js;
+    pp_follow fs;
+    memset(&js, 0, sizeof(js));
+    memset(&fs, 0, sizeof(fs));
+    if (jstate) js = *jstate;
+    if (fstate) fs = *fstate;
+    for (int64_t s = 0; s < o.S; s++)
+        ppepisode::episode_scene(T, seed, first_scene + s, s, *cfg, gap, o, tel->tab_valid, tel->tab_id,
+                                 (int)tel->tab_slots, tv, js, jstate != nullptr, fs, fstate != nullptr);
     return PP_OK;
 }
 

@@ -132,6 +132,7 @@ __device__ __forceinline__ unsigned long long trace_hwid() {
 #include "pp_synth.h"
 #include "pp_judge.h"
 #include "pp_follow.h"
+#include "pp_episode.h"
 
 using namespace ppd;
 
@@ -3169,6 +3170,21 @@ __global__ __launch_bounds__(256) void k_synth_traffic(ppsynth::LaneTables T, ui
         tb.tab_valid[(int64_t)j * o.S + s] = 0;
         if (tb.tab_id) tb.tab_id[(int64_t)j * o.S + s] = j;
     }
+}
+
+// Episode starts (include/pp.h pp_synth_episode; csrc/pp_episode.h): one lane per scene, every array
+// [k * S + s]; no LDS but ppg::atan2's table, no scratch (the per-lane cursors are indexed only in
+// unrolled select loops; the states come by value and go on by reference, never by address).
+// Runs once per episode: telemetry, car table, traffic, and the judge and follow states when given.
+__global__ __launch_bounds__(256) void k_synth_episode(ppsynth::LaneTables T, uint64_t seed, int64_t first,
+                                                       pp_episode_cfg cfg, pp_follow_cfg gap, ppsynth::OutBatch o,
+                                                       int32_t* tab_valid, int32_t* tab_id, int tab_slots,
+                                                       ppsynth::TrafficV tr, pp_judge js, int has_js, pp_follow fs,
+                                                       int has_fs) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= o.S) return;
+    ppepisode::episode_scene(T, seed, first + s, s, cfg, gap, o, tab_valid, tab_id, tab_slots, tr,
+                             js, has_js != 0, fs, has_fs != 0);
 }
 
 // ------------------------------------------------------------------------------------------------

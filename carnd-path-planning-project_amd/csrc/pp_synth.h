@@ -60,10 +60,13 @@ PP_HD inline void philox_round(uint32_t ctr[4], const uint32_t key[2]) {
     ctr[0] = n0; ctr[1] = lo1; ctr[2] = n2; ctr[3] = lo0;
 }
 
-// Philox4x32-10 block: counter (scene index lo/hi, block number, 0), key = seed.
-PP_HD inline void philox4x32(uint64_t seed, uint64_t scene, uint32_t block, uint32_t out[4]) {
+// Philox4x32-10 block: counter (scene index lo/hi, block number, tag), key = seed. The tag tells the
+// streams of different generators apart (kSceneTag: pp_synth_scenes'; csrc/pp_episode.h has its own).
+constexpr uint32_t kSceneTag = 0x5EED0001u;
+PP_HD inline void philox4x32(uint64_t seed, uint64_t scene, uint32_t block, uint32_t out[4],
+                             uint32_t tag = kSceneTag) {
     uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-    uint32_t ctr[4] = {(uint32_t)scene, (uint32_t)(scene >> 32), block, 0x5EED0001u};
+    uint32_t ctr[4] = {(uint32_t)scene, (uint32_t)(scene >> 32), block, tag};
     for (int r = 0; r < 10; r++) {
         philox_round(ctr, key);
         key[0] += 0x9E3779B9u;
@@ -130,12 +133,12 @@ PP_HD inline void mc_gauss4(uint64_t seed, uint64_t scene, int draw, int car, do
 
 struct Rng {
     uint64_t seed, scene;
-    uint32_t block;
+    uint32_t block, tag;
     uint32_t buf[4];
     int used;
-    PP_HD Rng(uint64_t s, uint64_t sc) : seed(s), scene(sc), block(0), used(4) {}
+    PP_HD Rng(uint64_t s, uint64_t sc, uint32_t tg = kSceneTag) : seed(s), scene(sc), block(0), tag(tg), used(4) {}
     PP_HD uint32_t next() {
-        if (used == 4) { philox4x32(seed, scene, block++, buf); used = 0; }
+        if (used == 4) { philox4x32(seed, scene, block++, buf, tag); used = 0; }
         return buf[used++];
     }
     // uniform in [0, 1): 53 random bits

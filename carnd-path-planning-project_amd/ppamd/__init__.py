@@ -142,6 +142,13 @@ class Follow(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in FOLLOW_FIELDS]
 
 
+class EpisodeCfg(C.Structure):
+    _fields_ = [("n_cars", C.c_int32), ("_pad", C.c_int32), ("ego_speed_min", C.c_double),
+                ("ego_speed_max", C.c_double), ("car_speed_min", C.c_double), ("car_speed_max", C.c_double),
+                ("ahead_share", C.c_double), ("extra_gap", C.c_double), ("offset_jitter", C.c_double),
+                ("gap_slack", C.c_double)]
+
+
 class Params(C.Structure):
     _fields_ = [("n_points", C.c_int32), ("n_speeds", C.c_int32), ("cost_mode", C.c_int32),
                 ("emit_paths", C.c_int32), ("speed_offsets", C.c_double * MAX_SPEEDS),
@@ -186,7 +193,8 @@ EXPORTS = ["pp_params_default", "pp_num_candidates", "pp_version", "pp_map_creat
            "pp_telemetry_parse_device", "pp_control_format_device", "pp_map_create_device",
            "pp_num_lanes", "pp_max_cars", "pp_libm_eval", "pp_debug_set", "pp_debug_get",
            "pp_judge_cfg_default", "pp_judge_frame", "pp_judge_frame_host", "pp_rollout_judged",
-           "pp_follow_cfg_default", "pp_traffic_follow", "pp_traffic_follow_host", "pp_rollout_reactive"]
+           "pp_follow_cfg_default", "pp_traffic_follow", "pp_traffic_follow_host", "pp_rollout_reactive",
+           "pp_episode_cfg_default", "pp_synth_episode", "pp_synth_episode_host"]
 
 
 def _load():
@@ -264,6 +272,16 @@ def _load():
     lib.pp_synth_traffic_host.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.POINTER(SceneBatch),
                                           C.POINTER(Traffic)]
     lib.pp_synth_traffic_host.restype = C.c_int32
+    lib.pp_episode_cfg_default.argtypes = [C.POINTER(EpisodeCfg)]
+    lib.pp_episode_cfg_default.restype = None
+    lib.pp_synth_episode.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.POINTER(EpisodeCfg), C.POINTER(FollowCfg),
+                                     C.POINTER(SceneBatch), C.POINTER(Traffic), C.POINTER(Judge), C.POINTER(Follow),
+                                     C.c_int32, C.c_void_p]
+    lib.pp_synth_episode.restype = C.c_int32
+    lib.pp_synth_episode_host.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.POINTER(EpisodeCfg),
+                                          C.POINTER(FollowCfg), C.POINTER(SceneBatch), C.POINTER(Traffic),
+                                          C.POINTER(Judge), C.POINTER(Follow)]
+    lib.pp_synth_episode_host.restype = C.c_int32
     lib.pp_plan_reset.argtypes = [C.c_void_p, C.c_int32]
     lib.pp_plan_reset.restype = C.c_int32
     lib.pp_telemetry_parse.argtypes = [C.c_char_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(SceneBatch),
@@ -478,6 +496,55 @@ def synth_traffic_host(m, S, seed=0x5EED0001, first=0, car_stride=12, slots=12):
     t = alloc_traffic(S)
     b, T = scene_struct(d), traffic_struct(t)
     _check(lib.pp_synth_traffic_host(m.handle, seed, first, C.byref(b), C.byref(T)), "pp_synth_traffic_host")
+    t["n_cars"] = T.n_cars
+    return d, t
+
+
+def default_episode_cfg(**over) -> EpisodeCfg:
+    """pp_episode_cfg_default, with fields overridden by keyword."""
+    c = EpisodeCfg()
+    lib.pp_episode_cfg_default(C.byref(c))
+    for k, v in over.items():
+        if k not in dict(EpisodeCfg._fields_):
+            raise KeyError(k)
+        setattr(c, k, v)
+    return c
+
+
+def _episode_args(S, cfg, xp, device, judge, follow):
+    cfg = cfg if cfg is not None else default_episode_cfg()
+    n = max(int(cfg.n_cars), 1)
+    if follow is not None:
+        assert follow["desired"].shape[0] >= int(cfg.n_cars), "follow state holds fewer cars than the episode"
+    d = add_car_table(alloc_scenes(S, max(n, 12), xp=xp, device=device), slots=max(n, 12), xp=xp, device=device)
+    t = alloc_traffic(S, n=max(n, 12), xp=xp, device=device)
+    J = judge_struct(judge) if judge is not None else None
+    F = follow_struct(follow) if follow is not None else None
+    return cfg, d, t, J, F
+
+
+def synth_episode(m, S, seed=0x5EED0001, first=0, cfg=None, fcfg=None, device=0, stream=None, judge=None,
+                  follow=None):
+    """pp_synth_episode: a drivable start state on the GPU, (scenes with an empty car table, traffic).
+    `judge` (alloc_judge) is made a warm state whose step numbers start at JUDGE_RING, `follow`
+    (alloc_follow) is reset; fcfg: the gap rule (None: default_follow_cfg)."""
+    import torch
+    cfg, d, t, J, F = _episode_args(S, cfg, "torch", torch.device("cuda", device), judge, follow)
+    b, T = scene_struct(d), traffic_struct(t)
+    _check(lib.pp_synth_episode(m.handle, seed, first, C.byref(cfg), C.byref(fcfg) if fcfg is not None else None,
+                                C.byref(b), C.byref(T), C.byref(J) if J is not None else None,
+                                C.byref(F) if F is not None else None, device, stream), "pp_synth_episode")
+    t["n_cars"] = T.n_cars
+    return d, t
+
+
+def synth_episode_host(m, S, seed=0x5EED0001, first=0, cfg=None, fcfg=None, judge=None, follow=None):
+    """pp_synth_episode_host: synth_episode on the host (numpy arrays, the same bits)."""
+    cfg, d, t, J, F = _episode_args(S, cfg, "numpy", None, judge, follow)
+    b, T = scene_struct(d), traffic_struct(t)
+    _check(lib.pp_synth_episode_host(m.handle, seed, first, C.byref(cfg), C.byref(fcfg) if fcfg is not None else None,
+                                     C.byref(b), C.byref(T), C.byref(J) if J is not None else None,
+                                     C.byref(F) if F is not None else None), "pp_synth_episode_host")
     t["n_cars"] = T.n_cars
     return d, t
 

@@ -447,6 +447,54 @@ int32_t pp_synth_traffic(pp_map* m, uint64_t seed, int64_t first_scene, pp_scene
 int32_t pp_synth_traffic_host(const pp_map* m, uint64_t seed, int64_t first_scene,
                               pp_scene_batch* telemetry, pp_traffic* out);
 
+/* ---- episode starts: start states made to be driven and judged ------------------------------- */
+/* pp_synth_traffic's scenes are the benchmark's snapshot: the previous path ends at the ego, the judge
+ * starts from v_0 = 0 and the cars are dropped with no regard to each other or to the ego, so the
+ * judge of a drive from them reports on the generator. pp_synth_episode writes a start that can be
+ * driven: the ego on a lane centre at speed ve along the segment's tangent u, its previous path the
+ * ten points p + (k + 1) ve 0.02 u AHEAD of it (n_prev = 0 at rest); n_cars cars placed one after the
+ * other, each on a random lane ahead of (probability ahead_share) or behind everything placed on that
+ * lane so far, the ego counting as present on every lane, at the net gap the car-following rule asks
+ * for, s*(follower, leader) of `gap_rule` (pp_follow_cfg above), plus gap_slack plus U[0, extra_gap);
+ * all of them reported in the frame-0 telemetry (ids 0..n_cars-1), the car table emptied. THIS
+ * LIBRARY'S OWN definitions (DESIGN.md "Episode starts" states them in full). A scene depends only
+ * on (seed, first_scene + s, cfg, gap_rule): shards concatenate; the stream is not pp_synth_scenes'.
+ *
+ * `jstate` (optional) becomes a WARM judge state: steps = PP_JUDGE_RING, every ring entry the start
+ * velocity ve u, head = u, seg_hint = the ego's segment, min_sep = +inf, every record 0. The judge
+ * takes it for a carried state, so a start at speed records no start transient. EPISODE STEP NUMBERS
+ * ARE THEREFORE OFFSET BY PP_JUDGE_RING: after F frames steps = PP_JUDGE_RING + F consume, and a
+ * first_step f is driven step f - PP_JUDGE_RING. `fstate` (optional) is reset for a fresh episode
+ * (started = 0, ego_seg = 0). */
+typedef struct pp_episode_cfg {
+    int32_t n_cars;          /* 12; 0 <= n_cars <= min(PP_MAX_CARS, car_stride, tab_slots)          */
+    int32_t _pad;
+    double  ego_speed_min;   /* 0 m/s                                                              */
+    double  ego_speed_max;   /* 20 m/s; both 0: every ego starts at rest                           */
+    double  car_speed_min;   /* 5 m/s                                                              */
+    double  car_speed_max;   /* 25 m/s                                                             */
+    double  ahead_share;     /* 0.75: probability that a car is placed ahead of the ego            */
+    double  extra_gap;       /* 40 m: U[0, extra_gap) on top of the required net gap               */
+    double  offset_jitter;   /* 0.3 m: lateral offset U(-j, j)                                     */
+    double  gap_slack;       /* 1e-6 m added to every required gap (covers the arcs' rounding)     */
+} pp_episode_cfg;            /* every field >= 0, min <= max, ahead_share <= 1                      */
+
+void    pp_episode_cfg_default(pp_episode_cfg* c);
+/* Device pointers; asynchronous on hip_stream. traffic's arrays hold at least cfg->n_cars cars;
+ * traffic->n_cars is set. gap_rule NULL: pp_follow_cfg_default. PP_ERR_ARG (before any HIP call) for
+ * a NULL, n_cars out of range, a bad cfg, a gap_rule pp_traffic_follow would refuse (or whose
+ * time_headway or min_gap is negative or NaN), or a ring too
+ * short for the traffic: (n_cars + 1) (s*(vmax, vmin) + gap_slack + extra_gap + max length) above the
+ * shortest lane's loop, vmax the larger speed maximum and vmin the smaller minimum (the defaults
+ * allow 33 cars on the highway map; denser traffic needs narrower speed ranges). */
+int32_t pp_synth_episode(pp_map* m, uint64_t seed, int64_t first_scene, const pp_episode_cfg* cfg,
+                         const pp_follow_cfg* gap_rule, pp_scene_batch* telemetry, pp_traffic* traffic,
+                         pp_judge* jstate, pp_follow* fstate, int32_t device, void* hip_stream);
+/* The same on the host (host pointers; the same arithmetic, bit for bit). */
+int32_t pp_synth_episode_host(const pp_map* m, uint64_t seed, int64_t first_scene, const pp_episode_cfg* cfg,
+                              const pp_follow_cfg* gap_rule, pp_scene_batch* telemetry, pp_traffic* traffic,
+                              pp_judge* jstate, pp_follow* fstate);
+
 /* A batch in HOST memory (the batched onMessage; what a server calls per tick): stages the
  * scenes — and their car table when tab_valid is set, updated in place — through device memory,
  * runs pp_eval on hip_stream and copies winner, n_out, next_x/next_y, cost and status back into
