@@ -11,7 +11,7 @@
 #include "../../include/pp.h"
 #include "pp_math.h"
 
-#ifndef PP_DIAGC   // branch-event census hook (pp_eval.hip, PP_DIAG builds)
+#ifndef PP_DIAGC   // branch-event census hook (pp_diag.h, PP_DIAG builds)
 #define PP_DIAGC(k, c) ((void)0)
 #endif
 

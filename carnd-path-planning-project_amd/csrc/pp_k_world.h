@@ -1,0 +1,222 @@
+// pp_k_world.h — device: what surrounds the evaluator. The closed-loop rollout's simulator shim, judge
+// and car-following traffic (k_sim, k_judge, k_follow), scene synthesis (k_synth*), the map tables'
+// kernels (Map::Init, src/main.cpp:89-131) and k_libm. Part of pp_eval.hip's translation unit.
+#pragma once
+
+// ------------------------------------------------------------------------------------------------
+// closed-loop rollout: the simulator shim (include/pp.h pp_rollout). One lane per scene: log the
+// frame, drive `consume` points of the plan, advance the traffic, report the cars in range.
+// ------------------------------------------------------------------------------------------------
+struct SimArgs {
+    int consume;
+    double range2;
+    int frame;
+    pp_rollout_log log;
+};
+
+__global__ __launch_bounds__(256) void k_sim(ppsynth::LaneTables LT, pp_scene_batch in,
+                                             ppsynth::TrafficV tr, pp_params P, pp_result out, SimArgs A) {
+    const int64_t S = in.n_scenes;
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const int N = P.n_points;
+    const int n_out = out.n_out[s];
+    const int T = out.winner[s] / P.n_speeds;
+    double* ex = (double*)in.ego_x;
+    double* ey = (double*)in.ego_y;
+    double* eyaw = (double*)in.ego_yaw_deg;
+    double* espd = (double*)in.ego_speed_mph;
+    double* px = (double*)in.prev_x;
+    double* py = (double*)in.prev_y;
+    const double x0 = ex[s], y0 = ey[s];
+    // frame record (the telemetry this frame was planned from + its plan)
+    const int64_t fs = (int64_t)A.frame * S + s;
+    if (A.log.ego_x) A.log.ego_x[fs] = x0;
+    if (A.log.ego_y) A.log.ego_y[fs] = y0;
+    if (A.log.ego_speed_mph) A.log.ego_speed_mph[fs] = espd[s];
+    if (A.log.target_lane) A.log.target_lane[fs] = T;
+    if (A.log.winner) A.log.winner[fs] = out.winner[s];
+    if (A.log.n_out) A.log.n_out[fs] = n_out;
+    if (A.log.status) A.log.status[fs] = out.status[s];
+    if (A.log.n_cars) A.log.n_cars[fs] = in.n_cars[s];
+    if (A.log.plan_x) {
+        for (int i = 0; i < N; i++) {
+            A.log.plan_x[((int64_t)A.frame * N + i) * S + s] = out.next_x[(int64_t)i * S + s];
+            A.log.plan_y[((int64_t)A.frame * N + i) * S + s] = out.next_y[(int64_t)i * S + s];
+        }
+    }
+    // ego: drive kk points; speed and yaw from the last driven step
+    const int kk = n_out < A.consume ? n_out : A.consume;
+    double nx = x0, ny = y0, qx = x0, qy = y0;
+    if (kk >= 1) { nx = out.next_x[(int64_t)(kk - 1) * S + s]; ny = out.next_y[(int64_t)(kk - 1) * S + s]; }
+    if (kk >= 2) { qx = out.next_x[(int64_t)(kk - 2) * S + s]; qy = out.next_y[(int64_t)(kk - 2) * S + s]; }
+    const double dx = nx - qx, dy = ny - qy;
+    const double dist = sqrt(dx * dx + dy * dy);
+    ex[s] = nx; ey[s] = ny;
+    espd[s] = dist * 50 * 2.237;
+    if (dist > 0) eyaw[s] = ppg::atan2(dy, dx) * 180.0 / kPi;
+    const int np = n_out - kk;
+    for (int i = 0; i < PP_PREV_KEEP; i++) {
+        const bool ok = i < np;
+        px[(int64_t)i * S + s] = ok ? out.next_x[(int64_t)(kk + i) * S + s] : 0.0;
+        py[(int64_t)i * S + s] = ok ? out.next_y[(int64_t)(kk + i) * S + s] : 0.0;
+    }
+    ((int32_t*)in.n_prev)[s] = np;
+    ((int32_t*)in.prev_target_lane)[s] = T;
+    // traffic: advance, then report the cars within range, ascending id
+    int nc = 0;
+    for (int j = 0; j < tr.n; j++) {
+        const int64_t tx = (int64_t)j * S + s;
+        const int lane = tr.lane[tx];
+        int seg = tr.seg[tx];
+        double t = tr.t[tx];
+        const double v = tr.v[tx];
+        ppsynth::lane_advance(LT, lane, &seg, &t, v * 0.02 * A.consume);
+        tr.seg[tx] = seg; tr.t[tx] = t;
+        double cx, cy, cvx, cvy;
+        ppsynth::traffic_car(LT, lane, seg, t, tr.off[tx], v, &cx, &cy, &cvx, &cvy);
+        const double rx = cx - nx, ry = cy - ny;
+        if (rx * rx + ry * ry <= A.range2 && nc < in.car_stride) {
+            const int64_t ix = (int64_t)nc * S + s;
+            ((int32_t*)in.car_id)[ix] = j;
+            ((double*)in.car_x)[ix] = cx; ((double*)in.car_y)[ix] = cy;
+            ((double*)in.car_vx)[ix] = cvx; ((double*)in.car_vy)[ix] = cvy;
+            nc++;
+        }
+    }
+    ((int32_t*)in.n_cars)[s] = nc;
+}
+
+// The rollout judge (include/pp.h pp_judge_frame; csrc/pp_judge.h): one lane per scene, every array
+// [k * S + s] so a wave's accesses are contiguous; no LDS, no scratch. Reads the pre-frame ego and
+// traffic and the frame's plan, so it runs between pp_eval and k_sim; writes only the judge state.
+__global__ __launch_bounds__(256) void k_judge(ppsynth::LaneTables LT, int64_t S, const double* ego_x,
+                                               const double* ego_y, const double* ego_yaw_deg,
+                                               const double* next_x, const double* next_y,
+                                               const int32_t* n_out, ppsynth::TrafficV tr, int consume,
+                                               pp_judge_cfg cfg, pp_judge st) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    ppjudge::judge_scene(LT, S, s, ego_x[s], ego_y[s], ego_yaw_deg[s], next_x, next_y, n_out[s], tr, consume,
+                         cfg, st);
+}
+
+// Reactive traffic (include/pp.h pp_traffic_follow; csrc/pp_follow.h): one lane per scene, every array
+// [k * S + s]; no LDS, no scratch. Reads the pre-frame ego and traffic, so it runs before k_judge and
+// k_sim; writes the traffic's speeds and the follow state.
+__global__ __launch_bounds__(256) void k_follow(ppsynth::LaneTables LT, ppfollow::ArcTables AT, int64_t S,
+                                                const double* ego_x, const double* ego_y,
+                                                const double* ego_speed_mph, ppsynth::TrafficV tr, int consume,
+                                                pp_follow_cfg cfg, pp_follow st) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    ppfollow::follow_scene(LT, AT, S, s, ego_x[s], ego_y[s], ego_speed_mph[s], tr, consume, cfg, st);
+}
+
+__global__ __launch_bounds__(256) void k_synth_traffic(ppsynth::LaneTables T, uint64_t seed, int64_t first,
+                                                       ppsynth::OutBatch o, ppsynth::TrafficV tr, pp_scene_batch tb) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= o.S) return;
+    ppsynth::synth_scene(T, seed, first + s, s, o, &tr);
+    for (int j = 0; tb.tab_valid && j < tb.tab_slots; j++) {       // empty table, slot j = car j
+        tb.tab_valid[(int64_t)j * o.S + s] = 0;
+        if (tb.tab_id) tb.tab_id[(int64_t)j * o.S + s] = j;
+    }
+}
+
+// Episode starts (include/pp.h pp_synth_episode; csrc/pp_episode.h): one lane per scene, every array
+// [k * S + s]; no LDS but ppg::atan2's table, no scratch (the per-lane cursors are indexed only in
+// unrolled select loops; the states come by value and go on by reference, never by address).
+// Runs once per episode: telemetry, car table, traffic, and the judge and follow states when given.
+__global__ __launch_bounds__(256) void k_synth_episode(ppsynth::LaneTables T, uint64_t seed, int64_t first,
+                                                       pp_episode_cfg cfg, pp_follow_cfg gap, ppsynth::OutBatch o,
+                                                       int32_t* tab_valid, int32_t* tab_id, int tab_slots,
+                                                       ppsynth::TrafficV tr, pp_judge js, int has_js, pp_follow fs,
+                                                       int has_fs) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= o.S) return;
+    ppepisode::episode_scene(T, seed, first + s, s, cfg, gap, o, tab_valid, tab_id, tab_slots, tr,
+                             js, has_js != 0, fs, has_fs != 0);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Map::Init on the device (src/main.cpp:89-131; pp_map_create_device). g: the MapG layout
+// (kMapArrays n: ref x/y, normal x/y, lane centres x[NL]/y[NL], lane lengths[NL]); t: the synth
+// lane tables (5 NL n). Three passes because each reads its neighbours' results of the previous one.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int wrap_i(int i, int n) { return i < 0 ? i + n : (i >= n ? i - n : i); }
+
+__global__ __launch_bounds__(256) void k_map_normals(const double* wx, const double* wy, int n, double* g,
+                                                     int* bad) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int p = wrap_i(i - 1, n);
+    const double dx = wx[i] - wx[p], dy = wy[i] - wy[p];
+    const double len = sqrt(dx * dx + dy * dy);
+    if (!(len > 0)) atomicOr(bad, 1);                 // duplicate consecutive waypoints
+    g[i] = wx[i]; g[n + i] = wy[i];
+    g[2 * n + i] = dy / len;
+    g[3 * n + i] = -dx / len;
+}
+
+__global__ __launch_bounds__(256) void k_map_lanes(int n, double* g) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int q = wrap_i(i + 1, n);
+    const double nx = g[2 * n + i], ny = g[3 * n + i];
+    double ax = (nx + g[2 * n + q]) / 2, ay = (ny + g[3 * n + q]) / 2;
+    // the host's std::atan2 / std::cos (glibc) restated bit for bit (pp_glibcm.h): the device map
+    // equals pp_map_create's (|a_avg - a_n| < pi, inside the restated cos domain)
+    const double a_n = ppg::atan2(ny, nx);
+    const double a_avg = ppg::atan2(ay, ax);
+    double c_;
+    if (!ppg::cos(a_avg - a_n, c_)) c_ = __builtin_nan("");
+    ax /= c_;
+    ay /= c_;
+    for (int r = 0; r < NL; r++) {
+        const double off = 4.0 * (r + 0.5);
+        g[(4 + r) * n + i] = g[i] + ax * off;
+        g[(4 + NL + r) * n + i] = g[n + i] + ay * off;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_map_lengths(int n, double* g, double* t) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int p = wrap_i(i - 1, n);
+    for (int r = 0; r < NL; r++) {
+        const double lx = g[(4 + r) * n + i], ly = g[(4 + NL + r) * n + i];
+        const double dx = lx - g[(4 + r) * n + p], dy = ly - g[(4 + NL + r) * n + p];
+        const double len = sqrt(dx * dx + dy * dy);
+        g[(4 + 2 * NL + r) * n + i] = len;                           // Map::get_lane_length
+        const double den = dx * dx + dy * dy;                         // helpers.h:202 rdenom
+        g[(4 + 3 * NL + r) * n + i] = den;
+        g[(4 + 4 * NL + r) * n + i] = 1.0 / den;
+        t[0 * NL * n + r * n + i] = lx;
+        t[1 * NL * n + r * n + i] = ly;
+        t[2 * NL * n + r * n + i] = len;
+        t[3 * NL * n + r * n + i] = dx / len;
+        t[4 * NL * n + r * n + i] = dy / len;
+    }
+}
+
+// the restated libm on the device (pp_libm_eval; parity tests of pp_glibcm.h's device build)
+__global__ __launch_bounds__(256) void k_libm(int kind, const double* a, const double* b, double* out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double r = __builtin_nan("");
+    if (kind == 0) ppg::sin(a[i], r);
+    else if (kind == 1) ppg::cos(a[i], r);
+    else r = ppg::atan2(a[i], b[i]);
+    out[i] = r;
+}
+
+// ------------------------------------------------------------------------------------------------
+// scene synthesis
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_synth(ppsynth::LaneTables T, uint64_t seed, int64_t first,
+                                               ppsynth::OutBatch o) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= o.S) return;
+    ppsynth::synth_scene(T, seed, first + s, s, o);
+}

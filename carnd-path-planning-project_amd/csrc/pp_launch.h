@@ -36,8 +36,6 @@ PrepV prep_bind(void* base, int64_t S) {
 std::atomic<int> g_dbg[PP_DBG_KEYS];
 int dbg(int key) { return g_dbg[key].load(std::memory_order_relaxed); }
 
-// K4 inside k_cand: the winners' sin/cos tables (2 N doubles each) fit the block's spline slots
-bool emit_in_ok(int N) { return 2 * N <= 5 * NL * kKP; }
 // small reference-mode batches (<= kFusedSmall scenes): K2 + K4 in one launch (k_cand_small) or the
 // whole step in one launch (k_step_small); PP_DBG_SHAPE forces one of the three shapes
 constexpr int64_t kFusedSmall = 16384;
@@ -215,14 +213,8 @@ void free_ws(StreamWS& W) {
 
 // k_cand's launch geometry for C candidates per scene (BPS == 1: SPB scenes per group; else one
 // scene over BPS groups of 256 candidates)
+// (lds: the block's LDS without the cost array, CandLds)
 struct CandGeom { int spb, bps, threads; size_t lds; int64_t groups; };
-// k_cand's LDS for SPB scenes per group: slots (5 x kKP doubles + 4 ints each), sFlags/sSlow,
-// then (8-aligned) sAdj and sNg
-size_t cand_geom_lds(int spb) {
-    const int nslot = NL * spb;
-    size_t lds = sizeof(double) * 5 * kKP * (size_t)nslot + sizeof(int) * 4 * nslot + sizeof(uint32_t) * 2 * spb;
-    return ((lds + 7) & ~(size_t)7) + sizeof(uint64_t) * 2 * spb + sizeof(int) * spb;
-}
 // the flat geometry for the all-paths mode (kMode 2): 256-lane groups over the batch's candidates,
 // scenes straddling two groups (their spline slots built in both, status flags merged with
 // atomics): four full waves per block where whole scenes would leave a wave slot of the CU idle
@@ -235,14 +227,14 @@ CandGeom cand_geom(int C, int64_t S, bool flat = false) {
         g.spb = (C + 254) / C + 1;
         g.bps = -1;
         g.threads = 256;
-        g.lds = cand_geom_lds(g.spb);
+        g.lds = CandLds{g.spb}.bytes();
         g.groups = (S * C + 255) / 256;
         return g;
     }
     g.spb = C <= 256 ? cands_per_block(C) : 1;
     g.bps = C <= 256 ? 1 : (C + 255) / 256;
     g.threads = C <= 256 ? ((g.spb * C + 63) / 64) * 64 : 256;
-    g.lds = cand_geom_lds(g.spb);
+    g.lds = CandLds{g.spb}.bytes();
     g.groups = g.bps == 1 ? (S + g.spb - 1) / g.spb : S * g.bps;
     return g;
 }
@@ -328,11 +320,11 @@ int32_t eval_plan(const pp_map* M, const pp_scene_batch* in, const pp_params* pr
     p.Cn = p.Dn * NL * prm->n_speeds;
     p.cg = cand_geom(p.Cn, p.S, prm->emit_paths && p.Dn == 1 && cand_flat_ok(p.Cn));
     if (p.cg.groups > 0x7fffffff) return PP_ERR_ARG;
-    p.fused = p.ref_direct && !prm->emit_paths && p.cg.bps == 1 && emit_in_ok(prm->n_points) && fused_small(p.S);
+    p.fused = p.ref_direct && !prm->emit_paths && p.cg.bps == 1 && CandLds{p.cg.spb}.replay_fits(prm->n_points) && fused_small(p.S);
     p.step_waves = step_waves_on(p.S, p.cg.spb, device);
     const size_t map_lds = sizeof(double) * (size_t)((kMapArrays * M->n + 1) & ~1);
     auto step_lds = [&](int wv, int spb) {
-        return map_lds + (wv != 0 ? sizeof(double) * (size_t)(cand_lds_doubles(spb) + kGeoD * spb) : cand_geom_lds(spb));
+        return map_lds + (wv != 0 ? sizeof(double) * (size_t)(CandLds{spb}.doubles() + kGeoD * spb) : CandLds{spb}.bytes());
     };
     if (p.step_waves && step_lds(p.step_waves, std::min(p.cg.spb, p.step_waves == 1 ? kStepWaveSpb : 16)) > 65536) p.step_waves = 0;
     p.spb_f = std::min(p.cg.spb, p.step_waves == 1 ? kStepWaveSpb : 256 / 16);
@@ -392,7 +384,7 @@ int32_t eval_bind(const pp_map* M, const DevState& DS, StreamWS& W, const pp_sce
         rc = ensure_rec(W, A.st, p.S);
         if (rc) return rc;
         A.wslot = rec_buf(W.rec);
-        A.cand_lds = ((p.cg.lds + 7) & ~(size_t)7) + sizeof(double) * 256;     // + sCost
+        A.cand_lds = CandLds{p.cg.spb}.bytes_cost();     // + sCost
     }
     A.pv = prep_bind(W.ws, W.ws_cap);
     A.mg.buf = DS.map;

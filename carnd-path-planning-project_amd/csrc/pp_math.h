@@ -64,7 +64,7 @@ __device__ __attribute__((noinline)) void sincos_large(double x, double* s, doub
 
 // sin and cos of x. Medium-size Cody-Waite reduction (3-part pi/2) for |x| <= 2^19 * pi/2;
 // beyond that the device library's reduction — compiled in only when kLarge (the hot loop is
-// instantiated without it: its arguments are bounded, see kSlowAngle in pp_eval.hip).
+// instantiated without it: its arguments are bounded, see kSlowAngle in pp_k_frame.h).
 constexpr double kMediumMax = 823549.6;   // < 2^19 * pi/2 (high word 0x413921fb)
 template <bool kLarge = true>
 __device__ __forceinline__ void sincos_pp(double x, double& s, double& c) {

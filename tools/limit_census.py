@@ -1,5 +1,5 @@
 """Limiter census on the GPU (the -DPP_LIMCENSUS build): one pp_eval over a
-BASELINE batch, then the census counters (csrc/pp_eval.hip PP_CEN events 26-33) as one JSON line.
+BASELINE batch, then the census counters (csrc/pp_diag.h PP_CEN, events 26-33 in csrc/pp_k_cand.h) as one JSON line.
 
 At every decision of the acceleration limiter (src/main.cpp:941 `acc + centrifugal_acceleration >
 maximum_acc`, and :972 after the speed override) the census build evaluates, from the same state,
