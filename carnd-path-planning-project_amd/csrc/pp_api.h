@@ -106,84 +106,63 @@ int32_t pp_map_create(const double* wx, const double* wy, int32_t n, pp_map** ou
 // Map::Init on the device from device waypoint arrays; the derived tables are mirrored to the host
 // (for pp_map_geometry, the host generator and other devices).
 static int32_t map_create_device(const double* d_wx, const double* d_wy, int32_t n, int32_t device,
-                                 void* hip_stream, pp_map** out);
-int32_t pp_map_create_device(const double* d_wx, const double* d_wy, int32_t n, int32_t device, void* hip_stream,
-                             pp_map** out) {
-    try { return map_create_device(d_wx, d_wy, n, device, hip_stream, out); } catch (...) { return PP_ERR_NOMEM; }
-}
-static int32_t map_create_device(const double* d_wx, const double* d_wy, int32_t n, int32_t device,
                                  void* hip_stream, pp_map** out) {
     if (!d_wx || !d_wy || !out || n < 3 || n > kMaxWaypoints || device < 0 || device >= kMaxDev) return PP_ERR_ARG;
-    pp_map* M = new (std::nothrow) pp_map();
+    DeviceGuard g(device);        // (declared first: the owners below are released on this device)
+    std::unique_ptr<pp_map> M(new (std::nothrow) pp_map());
     if (!M) return PP_ERR_NOMEM;
     M->n = n;
-    DeviceGuard g(device);
-    DevState& D = M->dev[device];
     hipStream_t st = (hipStream_t)hip_stream;
-    int* bad = nullptr;
-    if (hipMalloc(&D.map, sizeof(double) * kMapArrays * (size_t)n) != hipSuccess ||
-        hipMalloc(&D.lanetab, sizeof(double) * 5 * NL * (size_t)n) != hipSuccess || hipMalloc(&bad, sizeof(int)) != hipSuccess) {
-        if (D.map) (void)hipFree(D.map);
-        if (D.lanetab) (void)hipFree(D.lanetab);
-        delete M;
+    DevTables T;
+    DevMem<int> bad;
+    if (T.map.alloc(kMapArrays * (size_t)n) != PP_OK || T.lanetab.alloc(5 * NL * (size_t)n) != PP_OK ||
+        bad.alloc(1) != PP_OK)
         return PP_ERR_NOMEM;
-    }
+    // from here on the map kernels may be in flight: every exit, an exception's included, drains
+    // `st` before the buffers above are released (declared after them, so it runs first)
+    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};
     int rc = PP_OK;
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    if (hipMemsetAsync(bad, 0, sizeof(int), st) != hipSuccess) rc = PP_ERR_HIP;
-    hipLaunchKernelGGL(k_map_normals, dim3(blocks), dim3(256), 0, st, d_wx, d_wy, n, D.map, bad);
-    hipLaunchKernelGGL(k_map_lanes, dim3(blocks), dim3(256), 0, st, n, D.map);
-    hipLaunchKernelGGL(k_map_lengths, dim3(blocks), dim3(256), 0, st, n, D.map, D.lanetab);
+    if (hipMemsetAsync(bad.get(), 0, sizeof(int), st) != hipSuccess) rc = PP_ERR_HIP;
+    hipLaunchKernelGGL(k_map_normals, dim3(blocks), dim3(256), 0, st, d_wx, d_wy, n, T.map.get(), bad.get());
+    hipLaunchKernelGGL(k_map_lanes, dim3(blocks), dim3(256), 0, st, n, T.map.get());
+    hipLaunchKernelGGL(k_map_lengths, dim3(blocks), dim3(256), 0, st, n, T.map.get(), T.lanetab.get());
     if (hipGetLastError() != hipSuccess) rc = PP_ERR_HIP;
     int hbad = 0;
     M->geom.assign(kMapArrays * (size_t)n, 0.0);
     M->lanetab.assign(5 * NL * (size_t)n, 0.0);
-    if (rc == PP_OK && (hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipMemcpyAsync(M->geom.data(), D.map, sizeof(double) * kMapArrays * (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipMemcpyAsync(M->lanetab.data(), D.lanetab, sizeof(double) * 5 * NL * (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+    if (rc == PP_OK && (hipMemcpyAsync(&hbad, bad.get(), sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                        hipMemcpyAsync(M->geom.data(), T.map.get(), sizeof(double) * kMapArrays * (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                        hipMemcpyAsync(M->lanetab.data(), T.lanetab.get(), sizeof(double) * 5 * NL * (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess ||
                         hipStreamSynchronize(st) != hipSuccess))
         rc = PP_ERR_HIP;
-    (void)hipFree(bad);
     if (rc == PP_OK && hbad) rc = PP_ERR_ARG;          // Map::Init divides by a zero segment length
-    if (rc != PP_OK) {
-        (void)hipFree(D.map); (void)hipFree(D.lanetab);
-        D.map = D.lanetab = nullptr;
-        delete M;
-        return rc;
-    }
-    fill_ptab(M);
-    build_tables(M);
-    fill_arctab(M);
-    if (upload_wgrid(M, D) != PP_OK) {
-        free_map_tables(D);
-        (void)hipFree(D.map); (void)hipFree(D.lanetab);
-        delete M;
-        return PP_ERR_NOMEM;
-    }
-    D.init = true;
-    *out = M;
+    if (rc != PP_OK) return rc;
+    fill_ptab(M.get());
+    build_tables(M.get());
+    fill_arctab(M.get());
+    if (upload_wgrid(M.get(), T) != PP_OK) return PP_ERR_NOMEM;
+    M->dev[device].tab = std::move(T);
+    M->dev[device].init = true;
+    *out = M.release();
     return PP_OK;
 }
+int32_t pp_map_create_device(const double* d_wx, const double* d_wy, int32_t n, int32_t device, void* hip_stream,
+                             pp_map** out) {
+    try { return map_create_device(d_wx, d_wy, n, device, hip_stream, out); } catch (...) { return PP_ERR_NOMEM; }   // (host allocations)
+}
 
+// every device the runtime has, initialised for this map or not, in turn: made current, drained,
+// and its state released while it is current (the owners' destructors, which may run with another
+// device current, then find nothing left to do)
 int32_t pp_map_destroy(pp_map* M) {
     if (!M) return PP_ERR_ARG;
-    for (int d = 0; d < kMaxDev; d++) {
-        DevState& D = M->dev[d];
-        if (!D.init) continue;
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess) nd = 0;
+    for (int d = 0; d < nd && d < kMaxDev; d++) {
         DeviceGuard g(d);
         (void)hipDeviceSynchronize();
-        (void)hipFree(D.map); (void)hipFree(D.lanetab);
-        if (D.arctab) (void)hipFree(D.arctab);
-        free_map_tables(D);
-        for (auto& kv : D.sws) free_ws(kv.second);
-        D.sws.clear();
-        if (D.frame) (void)hipFree(D.frame);
-        if (D.frame_host) (void)hipHostFree(D.frame_host);
-        if (D.frame_stream) (void)hipStreamDestroy(D.frame_stream);
-        if (D.stage) (void)hipFree(D.stage);
-        if (D.stage_host) (void)hipHostFree(D.stage_host);
-        for (hipEvent_t e : D.ev_pool) (void)hipEventDestroy(e);
-        for (hipEvent_t e : D.ev_rec) (void)hipEventDestroy(e);
+        static_cast<DevRes&>(M->dev[d]) = DevRes();
     }
     delete M;
     return PP_OK;
@@ -203,10 +182,8 @@ int32_t pp_reserve(pp_map* M, int32_t device, int64_t max_scenes) {
     if (rc) return rc;
     StreamWS& W = M->dev[device].sws[nullptr];       // the null stream's workspace
     rc = ensure_ws(W, nullptr, max_scenes);
-    if (rc) return rc;
-    return ensure_rec(W, nullptr, max_scenes);
+    return rc ? rc : ensure_rec(W, nullptr, max_scenes);
 }
-
 
 int32_t pp_eval(pp_map* M, const pp_scene_batch* in, const pp_params* prm, pp_result* out,
                 int32_t device, void* hip_stream) {
@@ -241,12 +218,12 @@ int32_t pp_timing_enable(pp_map* M, int32_t device, int32_t enable) {
         // 2 per part when split) or 1,024 of all-kernel timing (4 per part); pp_eval takes the
         // events it records from this pool, pp_timing_read returns them
         DeviceGuard g(device);
-        const int rc = dev_init(M, device);       // (pp_map_destroy frees the events of initialised devices)
+        const int rc = dev_init(M, device);
         if (rc) return rc;
-        while (D.ev_pool.size() + D.ev_rec.size() < 4 * kSplitMax * 256) {
+        while (D.ev.pool.size() + D.ev.rec.size() < 4 * kSplitMax * 256) {
             hipEvent_t e;
             if (hipEventCreate(&e) != hipSuccess) return PP_ERR_HIP;
-            D.ev_pool.push_back(e);
+            D.ev.pool.push_back(e);
         }
     }
     return PP_OK;
@@ -260,7 +237,7 @@ int32_t pp_timing_read(pp_map* M, int32_t device, double* ms3, int64_t* launches
     for (int k = 0; k < 3; k++) { ms3[k] = 0; launches3[k] = 0; }
     int rc = PP_OK;
     constexpr int EG = 4 * kPartMax;
-    const size_t ng = D.ev_rec.size() / EG;
+    const size_t ng = D.ev.rec.size() / EG;
     // signed milliseconds from a to b (either order)
     auto dt = [&](hipEvent_t a, hipEvent_t b, float& t) {
         if (!a || !b) { rc = PP_ERR_HIP; return false; }
@@ -270,10 +247,10 @@ int32_t pp_timing_read(pp_map* M, int32_t device, double* ms3, int64_t* launches
         return false;
     };
     for (size_t i = 0; i < ng; i++) {
-        const int kind = D.ev_kind[i], parts = (kind >> 8) & 0xFF, np = parts ? parts : 1;
+        const int kind = D.ev.kind[i], parts = (kind >> 8) & 0xFF, np = parts ? parts : 1;
         const int per = (kind >> 16) & 0xF, pc = per ? per : np;    // parts per chunk
         const bool k2only = (kind & 16) != 0;
-        hipEvent_t* e0 = &D.ev_rec[EG * i];
+        hipEvent_t* e0 = &D.ev.rec[EG * i];
         for (int h = 0; h < np; h++) {
             hipEvent_t last = k2only ? e0[4 * h + 2] : e0[4 * h + 3];
             if (!last || hipEventSynchronize(last) != hipSuccess) rc = PP_ERR_HIP;
@@ -298,10 +275,10 @@ int32_t pp_timing_read(pp_map* M, int32_t device, double* ms3, int64_t* launches
             if (ok) { ms3[k] += sum; launches3[k]++; }
         }
         for (int k = 0; k < EG; k++)
-            if (D.ev_rec[EG * i + k]) D.ev_pool.push_back(D.ev_rec[EG * i + k]);
+            if (e0[k]) D.ev.pool.push_back(e0[k]);
     }
-    D.ev_rec.clear();
-    D.ev_kind.clear();
+    D.ev.rec.clear();
+    D.ev.kind.clear();
     return rc;
 }
 
@@ -316,7 +293,7 @@ int32_t pp_synth_scenes(pp_map* M, uint64_t seed, int64_t first_scene, pp_scene_
         std::lock_guard<std::mutex> lk(M->mu);
         const int rc = dev_init(M, device);
         if (rc) return rc;
-        T = lane_tables(M->dev[device].lanetab, M->n);
+        T = lane_tables(M->dev[device].tab.lanetab.get(), M->n);
     }
     const ppsynth::OutBatch o = out_batch(out);
     const int threads = 256;
@@ -347,7 +324,7 @@ int32_t pp_synth_traffic(pp_map* M, uint64_t seed, int64_t first_scene, pp_scene
         std::lock_guard<std::mutex> lk(M->mu);
         const int rc = dev_init(M, device);
         if (rc) return rc;
-        T = lane_tables(M->dev[device].lanetab, M->n);
+        T = lane_tables(M->dev[device].tab.lanetab.get(), M->n);
     }
     out->n_cars = ppsynth::kSynthCars;
     const ppsynth::OutBatch o = out_batch(tel);

@@ -45,17 +45,20 @@ int32_t pp_plan_batch_host(pp_map* M, int32_t device, pp_scene_batch* hin, const
         int rc = dev_init(M, device);
         if (rc) return rc;
         DevState& D = M->dev[device];
-        if (D.stage_cap < bytes) {
-            if (D.stage) { (void)hipDeviceSynchronize(); (void)hipFree(D.stage); D.stage = nullptr; D.stage_cap = 0; }
-            if (D.stage_host) { (void)hipHostFree(D.stage_host); D.stage_host = nullptr; }
-            if (hipMalloc(&D.stage, bytes) != hipSuccess) return PP_ERR_NOMEM;
-            if (hipHostMalloc(&D.stage_host, bytes, hipHostMallocDefault) != hipSuccess) {
-                (void)hipFree(D.stage); D.stage = nullptr; return PP_ERR_NOMEM;
-            }
-            D.stage_cap = bytes;
+        if (D.stage.cap() < (int64_t)bytes) {
+            // the old pair goes first, once the device has drained (earlier calls may have staged
+            // on any stream); the new buffers are kept only as a pair
+            if (D.stage) (void)hipDeviceSynchronize();
+            D.stage.reset(); D.stage_host.reset();
+            DevMem<> dev;
+            Pinned host;
+            rc = dev.grow(st, (int64_t)bytes, bytes);
+            if (!rc) rc = host.alloc(bytes, hipHostMallocDefault);
+            if (rc) return rc;
+            D.stage = std::move(dev); D.stage_host = std::move(host);
         }
-        base = (char*)D.stage;
-        mirror = (char*)D.stage_host;
+        base = (char*)D.stage.get();
+        mirror = (char*)D.stage_host.get();
     }
     double* dp = (double*)base;
     int32_t* ip = (int32_t*)(base + nd * 8);
@@ -227,19 +230,19 @@ int32_t pp_plan_frame(pp_map* M, int32_t device, double ego_x, double ego_y, dou
         int rc = dev_init(M, device);
         if (rc) return rc;
         // (both copies kFlagOff bytes: the 16-B units of the last fields may pass sizeof(Frame))
-        if (!DS.frame && hipMalloc(&DS.frame, kFlagOff) != hipSuccess) return PP_ERR_NOMEM;
+        if (DS.frame.grow(nullptr, 1, kFlagOff) != PP_OK) return PP_ERR_NOMEM;
         if (!DS.frame_host) {
-            if (hipHostMalloc(&DS.frame_host, kFlagOff + 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
+            if (DS.frame_host.alloc(kFlagOff + 64, hipHostMallocMapped | hipHostMallocCoherent) != PP_OK)
                 return PP_ERR_NOMEM;
-            memset(DS.frame_host, 0, kFlagOff + 64);
+            memset(DS.frame_host.get(), 0, kFlagOff + 64);
             DS.frame_seq = 0;
         }
-        if (!DS.frame_stream && hipStreamCreateWithFlags(&DS.frame_stream, hipStreamNonBlocking) != hipSuccess)
+        if (!DS.frame_stream && hipStreamCreateWithFlags(DS.frame_stream.out(), hipStreamNonBlocking) != hipSuccess)
             return PP_ERR_HIP;
-        d = (Frame*)DS.frame;
+        d = (Frame*)DS.frame.get();
     }
-    Frame& h = *(Frame*)DS.frame_host;
-    volatile uint32_t* flag = (volatile uint32_t*)((char*)DS.frame_host + kFlagOff);
+    Frame& h = *(Frame*)DS.frame_host.get();
+    volatile uint32_t* flag = (volatile uint32_t*)((char*)DS.frame_host.get() + kFlagOff);
     // (only the words the frame's ranges carry are written: the previous path's unused tail is
     // zeroed, every other input range is filled below)
     memset(h.px, 0, sizeof h.px); memset(h.py, 0, sizeof h.py);
@@ -261,7 +264,7 @@ int32_t pp_plan_frame(pp_map* M, int32_t device, double ego_x, double ego_y, dou
     if (nu > TS) return PP_ERR_ARG;                     // more than PP_MAX_CARS distinct cars
     const int nslots = DS.plan_table.layout(h.cid, nc, hs, 0, nu, poison);
     if (nslots < 0) return PP_ERR_ARG;
-    hipStream_t st = DS.frame_stream;
+    hipStream_t st = DS.frame_stream.get();
     pp_scene_batch B;
     memset(&B, 0, sizeof(B));
     B.n_scenes = 1; B.car_stride = PP_MAX_CARS;
@@ -331,7 +334,7 @@ int32_t pp_plan_frame(pp_map* M, int32_t device, double ego_x, double ego_y, dou
         }
     }
     void* hdev = nullptr;
-    if (hipHostGetDevicePointer(&hdev, DS.frame_host, 0) != hipSuccess) return PP_ERR_HIP;
+    if (hipHostGetDevicePointer(&hdev, DS.frame_host.get(), 0) != hipSuccess) return PP_ERR_HIP;
     io.h_in = (const uint4*)hdev; io.h_out = (uint4*)hdev; io.d_frame = (uint4*)d;
     io.h_flag = (uint32_t*)((char*)hdev + kFlagOff);
     io.seq = ++DS.frame_seq;

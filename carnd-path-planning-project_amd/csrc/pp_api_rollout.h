@@ -67,11 +67,11 @@ int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const 
         std::lock_guard<std::mutex> lk(M->mu);
         const int rc = dev_init(M, device);
         if (rc) return rc;
-        T = lane_tables(M->dev[device].lanetab, M->n);
+        T = lane_tables(M->dev[device].tab.lanetab.get(), M->n);
         if (fs) {
             const int ra = arc_init(M, device);
             if (ra) return ra;
-            AT = ppfollow::arc_tables(M->dev[device].arctab, M->n);
+            AT = ppfollow::arc_tables(M->dev[device].arctab.get(), M->n);
         }
     }
     SimArgs A;
@@ -142,7 +142,7 @@ int32_t pp_judge_frame(pp_map* M, const pp_scene_batch* tel, const pp_traffic* t
         std::lock_guard<std::mutex> lk(M->mu);
         const int rc = dev_init(M, device);
         if (rc) return rc;
-        T = lane_tables(M->dev[device].lanetab, M->n);
+        T = lane_tables(M->dev[device].tab.lanetab.get(), M->n);
     }
     launch_judge(T, tel, traffic_view(traffic, tel->n_scenes), plan, consume, cfg, state, (hipStream_t)hip_stream);
     if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
@@ -200,8 +200,8 @@ int32_t pp_traffic_follow(pp_map* M, const pp_scene_batch* tel, pp_traffic* traf
         if (rc) return rc;
         rc = arc_init(M, device);
         if (rc) return rc;
-        T = lane_tables(M->dev[device].lanetab, M->n);
-        AT = ppfollow::arc_tables(M->dev[device].arctab, M->n);
+        T = lane_tables(M->dev[device].tab.lanetab.get(), M->n);
+        AT = ppfollow::arc_tables(M->dev[device].arctab.get(), M->n);
     }
     launch_follow(T, AT, tel, traffic_view(traffic, tel->n_scenes), consume, cfg, state, (hipStream_t)hip_stream);
     if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
@@ -236,7 +236,7 @@ int32_t pp_synth_episode(pp_map* M, uint64_t seed, int64_t first_scene, const pp
         std::lock_guard<std::mutex> lk(M->mu);
         const int rc = dev_init(M, device);
         if (rc) return rc;
-        T = lane_tables(M->dev[device].lanetab, M->n);
+        T = lane_tables(M->dev[device].tab.lanetab.get(), M->n);
     }
     const ppsynth::OutBatch o = out_batch(tel);
     pp_judge js;

@@ -33,8 +33,10 @@
 #include <cstdlib>
 #include <cmath>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/pp.h"

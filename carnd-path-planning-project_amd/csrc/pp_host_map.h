@@ -1,5 +1,5 @@
-// pp_host_map.h — host: pp_map, per-device state, per-stream workspace, the map tables and their
-// upload. Part of pp_eval.hip's translation unit.
+// pp_host_map.h — host: the owners of device resources, pp_map, per-device state, per-stream
+// workspace, the map tables and their upload. Part of pp_eval.hip's translation unit.
 #pragma once
 
 // ================================================================================================
@@ -12,6 +12,79 @@ constexpr int kMaxWaypoints = 1 << 24;
 constexpr int kPrepD = 12 + 4 * NL;   // doubles per scene in PrepV (see prep_bind)
 constexpr int kPrepI = 7;
 
+// The owners of device resources. Each is move-only and releases what it holds in reset() and in its
+// destructor; nothing else in csrc/ frees device memory, pinned memory, a stream or an event.
+template <class H, hipError_t (*kRelease)(H)>
+class Owned {
+    H h_ = nullptr;
+public:
+    Owned() = default;
+    Owned(Owned&& o) noexcept { std::swap(h_, o.h_); }
+    Owned& operator=(Owned&& o) noexcept { std::swap(h_, o.h_); return *this; }   // (o releases the old one)
+    ~Owned() { reset(); }
+    H get() const { return h_; }
+    explicit operator bool() const { return h_ != nullptr; }
+    void reset() { if (h_) (void)kRelease(h_); h_ = nullptr; }
+    H* out() { reset(); return &h_; }          // for the runtime's create calls
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+struct Pinned : Owned<void*, hipHostFree> {     // pinned host memory
+    int alloc(size_t bytes, unsigned flags) {
+        void* p = nullptr;
+        const bool ok = hipHostMalloc(&p, bytes, flags) == hipSuccess;
+        *out() = ok ? p : nullptr;
+        if (!ok) (void)hipGetLastError();      // (as DevMem::grow)
+        return ok ? PP_OK : PP_ERR_NOMEM;
+    }
+};
+// device memory and the capacity it was grown to, in its user's unit (scenes, words, bytes): the two
+// change only together
+template <class T = void>
+class DevMem {
+    T* p_ = nullptr;
+    int64_t cap_ = 0;
+public:
+    DevMem() = default;
+    DevMem(DevMem&& o) noexcept { *this = std::move(o); }
+    DevMem& operator=(DevMem&& o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); return *this; }   // (o releases the old one)
+    ~DevMem() { reset(); }
+    T* get() const { return p_; }
+    int64_t cap() const { return cap_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; cap_ = 0; }
+    // at least `cap` units (`bytes` for that many): a buffer too small is released once `st`, the
+    // stream that uses it, has drained, and a new one made; its contents are not kept. A refused
+    // allocation leaves the owner empty and takes the runtime's last error with it, so the next
+    // call's launch check (hipGetLastError) does not report it.
+    int grow(hipStream_t st, int64_t cap, size_t bytes) {
+        if (cap_ >= cap) return PP_OK;
+        if (p_) { (void)hipStreamSynchronize(st); reset(); }
+        if (hipMalloc((void**)&p_, bytes) != hipSuccess) { p_ = nullptr; (void)hipGetLastError(); return PP_ERR_NOMEM; }
+        cap_ = cap;
+        return PP_OK;
+    }
+    int alloc(size_t n) { return grow(nullptr, (int64_t)n, sizeof(T) * n); }     // n elements, for an empty owner
+};
+// the timing events: the pool pp_eval takes from and the calls' records (raw handles: pp_timing_read
+// indexes them)
+struct EventSet {
+    std::vector<hipEvent_t> pool;
+    // groups of 4 kPartMax per pp_eval: before K1, after K1, after K2, after K3/K4 on the launch
+    // stream (the split: those four per part, each part's on its own stream, events 4 h .. 4 h + 3)
+    std::vector<hipEvent_t> rec;
+    // per group: bit 0 K3/K4 launched, bit 4 K2's events only, bit 5 no K1 kernel (the one-launch
+    // step), bits 8-15 the split's launched parts (0: none), bits 16-19 its parts per chunk (0: one chunk)
+    std::vector<int> kind;
+    EventSet() = default;
+    EventSet(EventSet&& o) noexcept { *this = std::move(o); }
+    EventSet& operator=(EventSet&& o) noexcept { pool.swap(o.pool); rec.swap(o.rec); kind.swap(o.kind); return *this; }
+    ~EventSet() {
+        for (auto* v : {&pool, &rec})
+            for (hipEvent_t e : *v) { Event own; *own.out() = e; }
+    }
+};
+
 // pp_eval's device workspaces, one set per HIP stream: evaluations on different streams never
 // share intermediate buffers, and evaluations on one stream are ordered by it. A buffer is grown
 // only after that stream has drained (it is the only stream using it).
@@ -21,45 +94,42 @@ constexpr int kSplitMax = 4;
 // (split_chunks); each part has its own flagged-group count word and 4 timing-event slots
 constexpr int kPartMax = 16;
 struct StreamWS {
-    void* ws = nullptr;           // prep workspace (per evaluation: scene x draw)
-    int64_t ws_cap = 0;
-    void* rec = nullptr;          // reference-mode winner record (per scene)
-    int64_t rec_cap = 0;
-    uint32_t* gbits = nullptr;    // k_cand groups holding a kLimSlow scene (bitmap; all zero between calls)
-    int64_t gbits_cap = 0;        // words
-    void* srt = nullptr;          // k_sort_cars' visit-major rows (SortedCars)
-    size_t srt_cap = 0;           // bytes
-    hipStream_t st2[kSplitMax - 1] = {};   // the split's other streams (shard-sized batches)
-    hipEvent_t fork = nullptr, join[kSplitMax - 1] = {};
+    DevMem<> ws;                  // prep workspace (capacity: evaluations, scene x draw)
+    DevMem<> rec;                 // reference-mode winner record (capacity: scenes)
+    DevMem<uint32_t> gbits;       // k_cand groups holding a kLimSlow scene (bitmap; all zero between calls; capacity: words)
+    DevMem<> srt;                 // k_sort_cars' visit-major rows (SortedCars; capacity: bytes)
+    Stream st2[kSplitMax - 1];    // the split's other streams (shard-sized batches)
+    Event fork, join[kSplitMax - 1];
 };
-struct DevState {
+// the device copies of the map's tables (dev_init, pp_map_create_device)
+struct DevTables {
+    DevMem<double> map;           // kMapArrays * n
+    DevMem<double> lanetab;       // synth tables: lc_x[NL n] lc_y[NL n] seg_len[NL n] tan_x[NL n] tan_y[NL n]
+    DevMem<uint2> wgrid;          // the closest-waypoint cell table (pp_map::wgrid)
+    DevMem<double2> wseg;         // reference segment lengths and reciprocals (pp_map::wseg)
+    DevMem<double> atab;          // the approach table (pp_map::atab)
+};
+// everything a map holds on one device. pp_map_destroy releases it by assigning an empty one while
+// the device is current and idle; init is true from the first successful dev_init on.
+struct DevRes {
     bool init = false;
-    double* map = nullptr;        // kMapArrays * n
-    uint2* wgrid = nullptr;       // the closest-waypoint cell table (pp_map::wgrid)
-    double2* wseg = nullptr;      // reference segment lengths and reciprocals (pp_map::wseg)
-    double* atab = nullptr;       // the approach table (pp_map::atab)
-    double* lanetab = nullptr;    // synth tables: lc_x[NL n] lc_y[NL n] seg_len[NL n] tan_x[NL n] tan_y[NL n]
-    double* arctab = nullptr;     // pp_map::arctab, uploaded on the first follow call (arc_init)
+    DevTables tab;
+    DevMem<double> arctab;        // pp_map::arctab, uploaded on the first follow call (arc_init)
     std::map<void*, StreamWS> sws;  // per hip_stream
-    void* frame = nullptr;        // single-frame scratch (pp_plan_frame)
-    void* frame_host = nullptr;   // its pinned host staging copy (coherent: k_plan_frame reads and
+    DevMem<> frame;               // single-frame scratch (pp_plan_frame)
+    Pinned frame_host;            // its pinned host staging copy (coherent: k_plan_frame reads and
                                   // writes it; the frame's done word follows the frame)
-    hipStream_t frame_stream = nullptr;  // pp_plan_frame's stream
+    Stream frame_stream;          // pp_plan_frame's stream
+    DevMem<> stage;               // pp_plan_batch_host staging buffer (capacity: bytes)
+    Pinned stage_host;            // its pinned host mirror (one copy per direction and region)
+    EventSet ev;
+};
+struct DevState : DevRes {
     uint32_t frame_seq = 0;       // the last frame's done word
     std::mutex frame_mu;          // one pp_plan_frame at a time per device (frame scratch + car table)
-    void* stage = nullptr;        // pp_plan_batch_host staging buffer
-    size_t stage_cap = 0;
-    void* stage_host = nullptr;   // its pinned host mirror (one copy per direction and region)
     std::mutex stage_mu;          // one pp_plan_batch_host at a time per device
     pptab::CarTable plan_table;   // pp_plan_frame's persistent car table (the reference's std::map)
     int timing = 0;               // pp_timing_enable: 0 off, 1 every kernel, 2 K2 only
-    std::vector<hipEvent_t> ev_pool;
-    // groups of 4 kPartMax per pp_eval: before K1, after K1, after K2, after K3/K4 on the launch
-    // stream (the split: those four per part, each part's on its own stream, events 4 h .. 4 h + 3)
-    std::vector<hipEvent_t> ev_rec;
-    // per group: bit 0 K3/K4 launched, bits 1-3 the split's parts (0: none), bit 4 K2's events only,
-    // bit 5 no K1 kernel (the one-launch step)
-    std::vector<int> ev_kind;
 };
 
 }  // namespace
@@ -257,32 +327,26 @@ void build_tables(pp_map* M) {
     try { build_atab(M); } catch (...) { M->atab.clear(); M->atab.shrink_to_fit(); }
 }
 
-void free_map_tables(DevState& D) {
-    if (D.wgrid) (void)hipFree(D.wgrid);
-    if (D.wseg) (void)hipFree(D.wseg);
-    if (D.atab) (void)hipFree(D.atab);
-    D.wgrid = nullptr; D.wseg = nullptr; D.atab = nullptr;
+// the device copy of a host array (an empty array: none). PP_ERR_NOMEM for the allocation,
+// PP_ERR_HIP for the copy; `d` holds the copy only on PP_OK
+template <class T>
+int upload(DevMem<T>& d, const std::vector<T>& h) {
+    d.reset();
+    if (h.empty()) return PP_OK;
+    const int rc = d.alloc(h.size());
+    if (rc) return rc;
+    if (hipMemcpy(d.get(), h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice) == hipSuccess) return PP_OK;
+    d.reset();
+    return PP_ERR_HIP;
 }
 
 // the device copies of the cell table, the segment table and the approach table (dev_init,
 // pp_map_create_device)
-int upload_wgrid(pp_map* M, DevState& D) {
-    if (!M->wgrid.empty()) {
-        if (hipMalloc(&D.wgrid, sizeof(uint2) * M->wgrid.size()) != hipSuccess) return PP_ERR_NOMEM;
-        if (hipMemcpy(D.wgrid, M->wgrid.data(), sizeof(uint2) * M->wgrid.size(), hipMemcpyHostToDevice) != hipSuccess)
-            return PP_ERR_HIP;
-    }
-    if (!M->wseg.empty()) {
-        if (hipMalloc(&D.wseg, sizeof(double2) * M->wseg.size()) != hipSuccess) return PP_ERR_NOMEM;
-        if (hipMemcpy(D.wseg, M->wseg.data(), sizeof(double2) * M->wseg.size(), hipMemcpyHostToDevice) != hipSuccess)
-            return PP_ERR_HIP;
-    }
-    if (!M->atab.empty()) {
-        if (hipMalloc(&D.atab, sizeof(double) * M->atab.size()) != hipSuccess) return PP_ERR_NOMEM;
-        if (hipMemcpy(D.atab, M->atab.data(), sizeof(double) * M->atab.size(), hipMemcpyHostToDevice) != hipSuccess)
-            return PP_ERR_HIP;
-    }
-    return PP_OK;
+int upload_wgrid(const pp_map* M, DevTables& T) {
+    int rc = upload(T.wgrid, M->wgrid);
+    if (!rc) rc = upload(T.wseg, M->wseg);
+    if (!rc) rc = upload(T.atab, M->atab);
+    return rc;
 }
 
 // Map::Init (src/main.cpp:89-131) + derived tables, on the host (done once per map).
@@ -403,12 +467,12 @@ ppsynth::LaneTables lane_tables(const double* t, int n) {
 int dev_init(pp_map* M, int device) {
     DevState& D = M->dev[device];
     if (D.init) return PP_OK;
-    if (hipMalloc(&D.map, sizeof(double) * M->geom.size()) != hipSuccess) return PP_ERR_NOMEM;
-    if (hipMalloc(&D.lanetab, sizeof(double) * M->lanetab.size()) != hipSuccess) return PP_ERR_NOMEM;
-    if (hipMemcpy(D.map, M->geom.data(), sizeof(double) * M->geom.size(), hipMemcpyHostToDevice) != hipSuccess) return PP_ERR_HIP;
-    if (hipMemcpy(D.lanetab, M->lanetab.data(), sizeof(double) * M->lanetab.size(), hipMemcpyHostToDevice) != hipSuccess) return PP_ERR_HIP;
-    const int rc = upload_wgrid(M, D);
-    if (rc != PP_OK) return rc;
+    DevTables T;                  // all or nothing: a failing return releases what was made
+    int rc = upload(T.map, M->geom);
+    if (!rc) rc = upload(T.lanetab, M->lanetab);
+    if (!rc) rc = upload_wgrid(M, T);
+    if (rc) return rc;
+    D.tab = std::move(T);
     D.init = true;
     return PP_OK;
 }
@@ -417,14 +481,7 @@ int dev_init(pp_map* M, int device) {
 // under M->mu)
 int arc_init(pp_map* M, int device) {
     DevState& D = M->dev[device];
-    if (D.arctab) return PP_OK;
-    if (hipMalloc(&D.arctab, sizeof(double) * M->arctab.size()) != hipSuccess) return PP_ERR_NOMEM;
-    if (hipMemcpy(D.arctab, M->arctab.data(), sizeof(double) * M->arctab.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(D.arctab);
-        D.arctab = nullptr;
-        return PP_ERR_HIP;
-    }
-    return PP_OK;
+    return D.arctab ? PP_OK : upload(D.arctab, M->arctab);
 }
 
 }  // namespace

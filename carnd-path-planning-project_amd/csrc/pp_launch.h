@@ -11,7 +11,6 @@ static_assert(kWinRec <= 3 * PP_MAX_POINTS + 2, "the stored winner slots share t
 double* rec_buf(void* rec) { return (double*)rec; }
 uint64_t* adj_buf(void* rec, int64_t cap) { return (uint64_t*)((double*)rec + 3 * PP_MAX_POINTS * cap); }
 
-
 PrepV prep_bind(void* base, int64_t S) {
     PrepV p;
     double* d = (double*)base;
@@ -147,25 +146,17 @@ int cands_per_block(int C) {
     return best;
 }
 
-// callers hold M->mu; `st` is the stream the workspace belongs to
-int ensure_ws(StreamWS& W, hipStream_t st, int64_t Sv) {
-    if (W.ws_cap >= Sv) return PP_OK;
-    if (W.ws) { (void)hipStreamSynchronize(st); (void)hipFree(W.ws); W.ws = nullptr; W.ws_cap = 0; }
-    if (hipMalloc(&W.ws, prep_bytes(Sv)) != hipSuccess) return PP_ERR_NOMEM;
-    W.ws_cap = Sv;
-    return PP_OK;
-}
+// callers hold M->mu; `st` is the stream the workspace belongs to (DevMem::grow drains it before
+// a buffer is replaced)
+int ensure_ws(StreamWS& W, hipStream_t st, int64_t Sv) { return W.ws.grow(st, Sv, prep_bytes(Sv)); }
 
 // k_sort_cars' output for S scenes of `rows` rows each (SortedCars over one allocation)
 size_t srt_bytes(int64_t S, int rows) { return (size_t)S * ((size_t)rows * (4 * sizeof(double) + sizeof(int)) + 8) + 256; }
 int ensure_srt(StreamWS& W, hipStream_t st, int64_t S, int rows, SortedCars& sc) {
     const size_t need = srt_bytes(S, rows);
-    if (W.srt_cap < need) {
-        if (W.srt) { (void)hipStreamSynchronize(st); (void)hipFree(W.srt); W.srt = nullptr; W.srt_cap = 0; }
-        if (hipMalloc(&W.srt, need) != hipSuccess) return PP_ERR_NOMEM;
-        W.srt_cap = need;
-    }
-    double* b = (double*)W.srt;
+    const int rc = W.srt.grow(st, (int64_t)need, need);
+    if (rc) return rc;
+    double* b = (double*)W.srt.get();
     const int64_t n = (int64_t)rows * S;
     sc.x = b; sc.y = b + n; sc.vx = b + 2 * n; sc.vy = b + 3 * n;
     sc.id = (int*)(b + 4 * n);
@@ -176,39 +167,23 @@ int ensure_srt(StreamWS& W, hipStream_t st, int64_t S, int rows, SortedCars& sc)
 
 int ensure_rec(StreamWS& W, hipStream_t st, int64_t S) {
     const int64_t cap = (S + 63) & ~(int64_t)63;   // whole 64-scene blocks
-    if (W.rec_cap >= cap) return PP_OK;
-    if (W.rec) { (void)hipStreamSynchronize(st); (void)hipFree(W.rec); W.rec = nullptr; W.rec_cap = 0; }
-    if (hipMalloc(&W.rec, rec_bytes(cap)) != hipSuccess) return PP_ERR_NOMEM;
-    W.rec_cap = cap;
-    return PP_OK;
+    return W.rec.grow(st, cap, rec_bytes(cap));
 }
 
 // The slow-group bitmap (words), then the flagged-group count and list (ngroups entries), in one
 // allocation: [cap words][count][list: 32 cap entries]
 int ensure_gbits(StreamWS& W, hipStream_t st, int64_t ngroups) {
     const int64_t words = (ngroups + 31) / 32;
-    if (W.gbits_cap >= words) return PP_OK;
-    if (W.gbits) { (void)hipStreamSynchronize(st); (void)hipFree(W.gbits); W.gbits = nullptr; W.gbits_cap = 0; }
+    if (W.gbits.cap() >= words) return PP_OK;
     const int64_t cap = std::max<int64_t>(words, 1024);
-    // [bits: cap words][flagged-group count][the split's second-half count][list: 32 cap entries]
+    // [bits: cap words][the parts' flagged-group counts: kPartMax words][list: 32 cap entries]
     const size_t bytes = sizeof(uint32_t) * (size_t)(cap + kPartMax + 32 * cap);
-    if (hipMalloc(&W.gbits, bytes) != hipSuccess) return PP_ERR_NOMEM;
-    if (hipMemsetAsync(W.gbits, 0, bytes, st) != hipSuccess) return PP_ERR_HIP;
-    W.gbits_cap = cap;
+    DevMem<uint32_t> g = std::move(W.gbits);       // (back only once it is cleared)
+    const int rc = g.grow(st, cap, bytes);
+    if (rc) return rc;
+    if (hipMemsetAsync(g.get(), 0, bytes, st) != hipSuccess) return PP_ERR_HIP;
+    W.gbits = std::move(g);
     return PP_OK;
-}
-
-void free_ws(StreamWS& W) {
-    for (int k = 0; k < kSplitMax - 1; k++) {
-        if (W.st2[k]) (void)hipStreamDestroy(W.st2[k]);
-        if (W.join[k]) (void)hipEventDestroy(W.join[k]);
-    }
-    if (W.fork) (void)hipEventDestroy(W.fork);
-    if (W.ws) (void)hipFree(W.ws);
-    if (W.rec) (void)hipFree(W.rec);
-    if (W.gbits) (void)hipFree(W.gbits);
-    if (W.srt) (void)hipFree(W.srt);
-    W = StreamWS();
 }
 
 // k_cand's launch geometry for C candidates per scene (BPS == 1: SPB scenes per group; else one
@@ -245,7 +220,6 @@ int n_draws(const pp_params* p) { return p->n_draws > 1 ? p->n_draws : 1; }
 size_t prep_lds_atab(int n) {
     return sizeof(double) * (((kMapArrays * (size_t)n + 1) & ~(size_t)1) + kAtabD * (size_t)n);
 }
-
 
 bool params_ok(const pp_params* p) {
     return p && p->n_points > PP_PREV_KEEP && p->n_points <= PP_MAX_POINTS && p->n_speeds >= 1 &&
@@ -304,7 +278,7 @@ struct EvalPlan {
     int prep_g;               // K1 lanes per evaluation (prep_group)
     bool need_rec;            // the winner record (k_cand -> k_emit, or inside the fused kernels)
     // comfort mode without paths or draws, every scene's candidates in one block: k_cand makes the
-    // decision and stores the winner's spline slot in the record's memory (616 B per scene of its
+    // decision and stores the winner's spline slot in the record's memory (kWinRec x 8 = 624 B per scene of its
     // 3,088), k_winner_st re-runs the winner from it
     bool need_wslot;
     // K0 (k_sort_cars) ahead of the one-lane K1: no car table, fewer than kSortDmax draws, at
@@ -372,8 +346,8 @@ int32_t eval_bind(const pp_map* M, const DevState& DS, StreamWS& W, const pp_sce
     if (p.need_rec) {
         rc = ensure_rec(W, A.st, p.S);
         if (rc) return rc;
-        A.rec = rec_buf(W.rec);
-        A.adjm = adj_buf(W.rec, W.rec_cap);
+        A.rec = rec_buf(W.rec.get());
+        A.adjm = adj_buf(W.rec.get(), W.rec.cap());
     }
     if (p.need_srt) {
         rc = ensure_srt(W, A.st, p.S, in->car_stride, A.srt);
@@ -383,25 +357,25 @@ int32_t eval_bind(const pp_map* M, const DevState& DS, StreamWS& W, const pp_sce
     if (p.need_wslot) {
         rc = ensure_rec(W, A.st, p.S);
         if (rc) return rc;
-        A.wslot = rec_buf(W.rec);
+        A.wslot = rec_buf(W.rec.get());
         A.cand_lds = CandLds{p.cg.spb}.bytes_cost();     // + sCost
     }
-    A.pv = prep_bind(W.ws, W.ws_cap);
-    A.mg.buf = DS.map;
+    A.pv = prep_bind(W.ws.get(), W.ws.cap());
+    A.mg.buf = DS.tab.map.get();
     A.mg.n = M->n;
     A.mg.fastm = M->fastm;
     A.mg.wg = M->wg;
-    A.mg.wg.cells = DS.wgrid;
-    A.mg.wseg = DS.wseg;
-    A.mg.atab = DS.atab;
+    A.mg.wg.cells = DS.tab.wgrid.get();
+    A.mg.wseg = DS.tab.wseg.get();
+    A.mg.atab = DS.tab.atab.get();
     // k_prep<true, false> stages the approach table after the map where both fit a block's 64 KB
-    A.mg.atab_lds = DS.atab && prep_lds_atab(M->n) <= 65536;
+    A.mg.atab_lds = DS.tab.atab && prep_lds_atab(M->n) <= 65536;
     A.P = *prm;
     A.B = *in;
     A.R = *out;
     if (!A.P.emit_paths) { A.R.paths = nullptr; A.R.path_len = nullptr; }
-    A.gb.bits = W.gbits; A.gb.SPB = p.cg.spb; A.gb.BPS = p.cg.bps; A.gb.C = p.Cn;
-    A.gb.count = W.gbits + W.gbits_cap;
+    A.gb.bits = W.gbits.get(); A.gb.SPB = p.cg.spb; A.gb.BPS = p.cg.bps; A.gb.C = p.Cn;
+    A.gb.count = W.gbits.get() + W.gbits.cap();
     A.gb.list = A.gb.count + kPartMax;
     return PP_OK;
 }
@@ -415,15 +389,15 @@ int32_t poison_fill(const StreamWS& W, hipStream_t st, const EvalPlan& p, const 
     const int64_t S = p.S, Cn = p.Cn, N = prm->n_points;
     const int64_t words = (p.cg.groups + 31) / 32;
     std::vector<uint32_t> hb((size_t)words);
-    if (hipMemcpyAsync(hb.data(), W.gbits, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, st) != hipSuccess ||
+    if (hipMemcpyAsync(hb.data(), W.gbits.get(), sizeof(uint32_t) * words, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
         return PP_ERR_HIP;
     for (uint32_t w : hb)
         if (w) return PP_ERR_STATE;
-    const bool ok = fill(W.ws, prep_bytes(W.ws_cap)) &&
-                    fill(W.rec, W.rec ? rec_bytes(W.rec_cap) : 0) &&
-                    fill(W.srt, W.srt ? W.srt_cap : 0) &&
-                    fill(W.gbits + W.gbits_cap + kPartMax, sizeof(uint32_t) * 32 * (size_t)W.gbits_cap) &&
+    const bool ok = fill(W.ws.get(), prep_bytes(W.ws.cap())) &&
+                    fill(W.rec.get(), W.rec ? rec_bytes(W.rec.cap()) : 0) &&
+                    fill(W.srt.get(), (size_t)W.srt.cap()) &&
+                    fill(W.gbits.get() + W.gbits.cap() + kPartMax, sizeof(uint32_t) * 32 * (size_t)W.gbits.cap()) &&
                     fill(out->winner, 4 * S) && fill(out->n_out, 4 * S) && fill(out->status, 4 * S) &&
                     fill(out->next_x, 8 * N * S) && fill(out->next_y, 8 * N * S) &&
                     fill(out->cost, 8 * Cn * S) && fill(out->info, sizeof(pp_scene_info) * S) &&
@@ -443,8 +417,8 @@ int32_t check_limits(const StreamWS& W, const EvalPlan& p, const EvalArgs& A) {
     const long long Cn = p.Cn;
     L.paths = A.R.paths; L.npaths = A.R.paths ? (long long)p.S * A.P.n_points * Cn * 2 : 0;
     L.nx = A.R.next_x; L.ny = A.R.next_y; L.nnext = (long long)p.S * A.P.n_points;
-    L.rec = A.rec; L.nrec = A.rec ? 3LL * PP_MAX_POINTS * W.rec_cap : 0;
-    L.adjm = (const unsigned long long*)A.adjm; L.nadj = A.adjm ? 2LL * W.rec_cap : 0;
+    L.rec = A.rec; L.nrec = A.rec ? 3LL * PP_MAX_POINTS * W.rec.cap() : 0;
+    L.adjm = (const unsigned long long*)A.adjm; L.nadj = A.adjm ? 2LL * W.rec.cap() : 0;
     L.cost = A.R.cost; L.ncost = (long long)p.S * Cn; L.nscen = p.S;
     if (hipDeviceSynchronize() != hipSuccess ||
         hipMemcpyToSymbol(HIP_SYMBOL(g_lim), &L, sizeof L) != hipSuccess) return PP_ERR_HIP;
@@ -459,10 +433,10 @@ int32_t check_limits(const StreamWS& W, const EvalPlan& p, const EvalArgs& A) {
 struct EvalEvents { DevState* DS; size_t base; bool timing, tall, tk2; };
 hipEvent_t ev_at(const EvalEvents& E, int i) {
     DevState& DS = *E.DS;
-    hipEvent_t& e = DS.ev_rec[E.base + i];
+    hipEvent_t& e = DS.ev.rec[E.base + i];
     if (!e) {
-        if (DS.ev_pool.empty() && hipEventCreate(&e) != hipSuccess) return nullptr;
-        if (!e) { e = DS.ev_pool.back(); DS.ev_pool.pop_back(); }
+        if (DS.ev.pool.empty() && hipEventCreate(&e) != hipSuccess) return nullptr;
+        if (!e) { e = DS.ev.pool.back(); DS.ev.pool.pop_back(); }
     }
     return e;
 }
@@ -470,7 +444,7 @@ hipEvent_t ev_at(const EvalEvents& E, int i) {
 // The one-launch step (k_step_small, k_step_small512; fio: k_plan_frame)
 int32_t launch_step(const EvalArgs& A, const EvalPlan& p, const EvalEvents& E, const FrameIO* fio) {
     hipStream_t st = A.st;
-    if (E.timing) E.DS->ev_kind.back() |= 32;          // (no K1 kernel: K1 runs inside the step)
+    if (E.timing) E.DS->ev.kind.back() |= 32;          // (no K1 kernel: K1 runs inside the step)
     if (E.tall) (void)hipEventRecord(ev_at(E, 0), st);
     // K1 takes 16 lanes for each of the block's spb_f scenes, K2 spb_f x C lanes: the block needs
     // both (C <= 9 gives cg.threads < 16 spb_f; the K1 of the scenes beyond would not run)
@@ -559,22 +533,22 @@ int32_t launch_split(const EvalArgs& A, const EvalPlan& p, const EvalEvents& E, 
     const CandGeom& cg = p.cg;
     const int64_t S = p.S;
     const int NS = split_parts(S), NC = split_chunks(S), NT = NS * NC;
-    if (!W.fork && hipEventCreateWithFlags(&W.fork, hipEventDisableTiming) != hipSuccess) return PP_ERR_HIP;
+    if (!W.fork && hipEventCreateWithFlags(W.fork.out(), hipEventDisableTiming) != hipSuccess) return PP_ERR_HIP;
     for (int k = 0; k < NS - 1; k++)
-        if (!W.st2[k] && (hipStreamCreateWithFlags(&W.st2[k], hipStreamNonBlocking) != hipSuccess ||
-                          hipEventCreateWithFlags(&W.join[k], hipEventDisableTiming) != hipSuccess))
+        if ((!W.st2[k] && hipStreamCreateWithFlags(W.st2[k].out(), hipStreamNonBlocking) != hipSuccess) ||
+            (!W.join[k] && hipEventCreateWithFlags(W.join[k].out(), hipEventDisableTiming) != hipSuccess))
             return PP_ERR_HIP;
     const int64_t G = cg.groups;
     const PrepLds L = prep_lds(A.mg);
     int launched = 0;     // parts launched (an empty part is skipped; never at >= 2,048 scenes)
     for (int c = 0; c < NC; c++) {
         // fork: the chunk's other streams start behind everything before it on the caller's stream
-        if (hipEventRecord(W.fork, st) != hipSuccess) return PP_ERR_HIP;
+        if (hipEventRecord(W.fork.get(), st) != hipSuccess) return PP_ERR_HIP;
         for (int k = 0; k < NS - 1; k++)
-            if (hipStreamWaitEvent(W.st2[k], W.fork, 0) != hipSuccess) return PP_ERR_HIP;
+            if (hipStreamWaitEvent(W.st2[k].get(), W.fork.get(), 0) != hipSuccess) return PP_ERR_HIP;
         for (int h = 0; h < NS; h++) {
             const int t = c * NS + h;
-            hipStream_t sh = h == 0 ? st : W.st2[h - 1];
+            hipStream_t sh = h == 0 ? st : W.st2[h - 1].get();
             const int64_t g0 = G * t / NT, g1 = G * (t + 1) / NT;
             const int64_t v0 = std::min<int64_t>(S, g0 * cg.spb), v1 = std::min<int64_t>(S, g1 * cg.spb);
             if (v1 <= v0) continue;
@@ -597,11 +571,11 @@ int32_t launch_split(const EvalArgs& A, const EvalPlan& p, const EvalEvents& E, 
         }
         // join: the caller's stream waits for the chunk's other streams
         for (int k = 0; k < NS - 1; k++)
-            if (hipEventRecord(W.join[k], W.st2[k]) != hipSuccess || hipStreamWaitEvent(st, W.join[k], 0) != hipSuccess)
+            if (hipEventRecord(W.join[k].get(), W.st2[k].get()) != hipSuccess || hipStreamWaitEvent(st, W.join[k].get(), 0) != hipSuccess)
                 return PP_ERR_HIP;
     }
     // (the timing record: parts launched, and parts per chunk for the per-chunk spans)
-    if (E.timing) E.DS->ev_kind.back() |= (launched << 8) | (NC > 1 ? NS << 16 : 0);
+    if (E.timing) E.DS->ev.kind.back() |= (launched << 8) | (NC > 1 ? NS << 16 : 0);
     g_dbg[PP_DBG_LAST_PARTS].store(launched, std::memory_order_relaxed);
     if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
     return PP_OK;
@@ -696,11 +670,11 @@ int32_t eval_impl(pp_map* M, const pp_scene_batch* in, const pp_params* prm, pp_
         rc = poison_fill(W, A.st, p, prm, out);
         if (rc) return rc;
     }
-    EvalEvents E = {&DS, DS.ev_rec.size(), DS.timing != 0, DS.timing == 1, DS.timing != 0};
+    EvalEvents E = {&DS, DS.ev.rec.size(), DS.timing != 0, DS.timing == 1, DS.timing != 0};
     if (E.timing) {
-        DS.ev_rec.resize(E.base + 4 * kPartMax, nullptr);
+        DS.ev.rec.resize(E.base + 4 * kPartMax, nullptr);
         // (bit 0: K4 is a kernel of its own, neither all paths nor inside the fused kernels)
-        DS.ev_kind.push_back((!(p.ref_direct && prm->emit_paths) && !p.fused ? 1 : 0) | (E.tall ? 0 : 16));
+        DS.ev.kind.push_back((!(p.ref_direct && prm->emit_paths) && !p.fused ? 1 : 0) | (E.tall ? 0 : 16));
     }
 #ifdef PP_CHECK
     rc = check_limits(W, p, A);
