@@ -90,6 +90,23 @@ int32_t pp_libm_eval(int32_t kind, const double* a, const double* b, double* out
     return hipGetLastError() == hipSuccess ? PP_OK : PP_ERR_HIP;
 }
 
+int32_t pp_math_eval(int32_t kind, const double* a, const double* b, const double* c, const double* d,
+                     double* out0, double* out1, double* out2, int64_t n, int32_t device, void* hip_stream) {
+    const MathArity ar = math_arity(kind);
+    if (kind < 0 || kind >= PP_MATH_KINDS || ar.nin == 0 || n < 0 || device < 0 || device >= kMaxDev) return PP_ERR_ARG;
+    const double* in[4] = {a, b, c, d};
+    double* out[3] = {out0, out1, out2};
+    for (int k = 0; k < ar.nin && n > 0; k++) if (!in[k]) return PP_ERR_ARG;
+    for (int k = 0; k < ar.nout && n > 0; k++) if (!out[k]) return PP_ERR_ARG;
+    if (n == 0) return PP_OK;
+    DeviceGuard g(device);
+    const int64_t blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffff) return PP_ERR_ARG;
+    hipLaunchKernelGGL(k_math, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, kind, a, b, c, d,
+                       out0, out1, out2, n);
+    return hipGetLastError() == hipSuccess ? PP_OK : PP_ERR_HIP;
+}
+
 const char* pp_version(void) { return "pp-mi355x 0.1 (gfx950, fp64, lane-per-candidate)"; }
 
 int32_t pp_map_create(const double* wx, const double* wy, int32_t n, pp_map** out) {

@@ -19,7 +19,7 @@
 // output frame, winner record and map staging (pp_k_frame.h); K0/K1 scene preparation
 // (pp_k_prep.h); phase A's spline slots (pp_k_spline.h); K2 candidates (pp_k_cand.h); K3/K4 output
 // (pp_k_out.h); the fused small-batch and frame kernels (pp_k_step.h); rollout, synthesis, map and
-// libm kernels (pp_k_world.h). Then the host side (pp_host_map.h, pp_launch.h, pp_api.h,
+// libm kernels (pp_k_world.h); the primitives' test kernel (pp_k_math.h). Then the host side (pp_host_map.h, pp_launch.h, pp_api.h,
 // pp_api_rollout.h, pp_api_frame.h).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -59,6 +59,7 @@ using namespace ppd;
 #include "pp_k_out.h"        // K3/K4: k_winner, k_winner_st, k_emit
 #include "pp_k_step.h"       // k_cand_small, k_step_small(512), k_plan_frame
 #include "pp_k_world.h"      // k_sim, k_judge, k_follow, k_synth*, map kernels, k_libm
+#include "pp_k_math.h"       // k_math: the loop's FP64 primitives over arrays (pp_math_eval)
 
 // ================================================================================================
 // host side (one translation unit with the kernels above, so the launches see them)

@@ -69,7 +69,9 @@ __device__ __forceinline__ double turn_angle(double nc, double speed, double adi
     if (adiff < 0) nad *= -1;
     return nad - adiff;
 }
-// sin and cos of a turn: fdlibm's kernel polynomials in fused form (~1 ulp) on [-pi/4, pi/4]; a
+// sin and cos of a turn: fdlibm's kernel polynomials in fused form on [-pi/4, pi/4] (< 1 ulp,
+// tests/test_math_primitives.py; cos keeps the rounding error of 1 - z/2 as fdlibm's does: without
+// it 1.19 ulp); a
 // wider turn (rare: a wide step turn, or a step slower than ~0.7 m/s) is first reduced by the
 // nearest multiple of pi/2 (two-part Cody-Waite: |error| < 1e-15 rad up to kMediumMax, plenty for an
 // output frame) and its quadrant applied after; beyond kMediumMax (only from an absurd telemetry
@@ -106,7 +108,9 @@ __device__ __forceinline__ void turn_sincos(double r, double& s, double& c) {
     pc = __builtin_fma(z, pc, kc(-1.38888888888741095749e-03));
     pc = __builtin_fma(z, pc, kc(4.16666666666666019037e-02));
     s = __builtin_fma(y * z, ps, y);
-    c = __builtin_fma(z * z, pc, __builtin_fma(-0.5, z, 1.0));
+    // 1 - z/2 rounds: its error (1 - w) - hz is exact and joins the small term, as in fdlibm's kernel
+    const double hz = 0.5 * z, w = 1.0 - hz;
+    c = w + __builtin_fma(z * z, pc, (1.0 - w) - hz);
     if (__builtin_expect(q != 0, 0)) {
         if (q & 1) { const double t = s; s = c; c = -t; }
         if (q & 2) { s = -s; c = -c; }

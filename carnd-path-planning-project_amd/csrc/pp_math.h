@@ -4,8 +4,11 @@
 // atan2 a wide argument-reduction tree: together ~80 VGPRs of the loop's register peak (measured
 // with -Rpass-analysis=kernel-resource-usage), which halves occupancy. The planner only feeds them
 // small arguments (headings and turn angles), so these are the classic fdlibm-style algorithms
-// (Cody-Waite reduction by pi/2, minimax kernels, atan with 4-interval reduction), < 1 ulp like
-// glibc's, with the rare large-argument case handed to the device library in a non-inlined call.
+// (Cody-Waite reduction by pi/2, minimax kernels, atan with 4-interval reduction), with the rare
+// large-argument case handed to the device library in a non-inlined call. Measured against exact
+// references (tests/test_math_primitives.py, profiles/math_primitives.json): sin and cos < 1 ulp
+// (0.78); atan2_fast / atan2_unit < 1 ulp (atan2_core's compensated reduction); atan2_pp, fdlibm's
+// form, which divides first, 1.23 ulp: only zero and non-finite arguments reach it (exact values).
 // All arithmetic is plain IEEE double (the library is built with -ffp-contract=off).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -62,10 +65,12 @@ __device__ __attribute__((noinline)) void sincos_large(double x, double* s, doub
     *c = cos(x);
 }
 
-// sin and cos of x. Medium-size Cody-Waite reduction (3-part pi/2) for |x| <= 2^19 * pi/2;
+// sin and cos of x. Medium-size Cody-Waite reduction (3-part pi/2) for |x| <~ 2^20 * pi/2;
 // beyond that the device library's reduction — compiled in only when kLarge (the hot loop is
 // instantiated without it: its arguments are bounded, see kSlowAngle in pp_k_frame.h).
-constexpr double kMediumMax = 823549.6;   // < 2^19 * pi/2 (high word 0x413921fb)
+// (the reduction below runs for high words up to 0x413921fb, |x| <~ 2^20 * pi/2, as fdlibm's does;
+// kMediumMax, < 2^19 * pi/2, bounds turn_sincos's two-part reduction in pp_k_frame.h)
+constexpr double kMediumMax = 823549.6;
 template <bool kLarge = true>
 __device__ __forceinline__ void sincos_pp(double x, double& s, double& c) {
     const int hx = hiword(x);
@@ -202,37 +207,56 @@ __device__ __forceinline__ double atan2_pp(double y, double x) {
     }
 }
 
-// Branch-free atan2 for finite nonzero (y, x): ONE division and no divergent interval branches.
-// The argument reduction of atan_pos is applied to (|y|, |x|) directly — e.g. t = (|y|-|x|) /
-// (|x|+|y|) instead of (q-1)/(q+1) with a rounded q = |y|/|x| — so the reduced argument carries a
-// single rounding (slightly more accurate than the two-division form). Interval selection by
-// exact comparisons of |y| against 7/16, 11/16, 19/16, 39/16 times |x| (scaled by 16, exact in
-// double for the magnitudes that reach this path); the quadrant logic is atan2_pp's.
-__device__ __forceinline__ double atan2_fast(double y, double x) {
-    const double pi = 3.1415926535897931160E+00, pi_lo = 1.2246467991473531772E-16;
-    const int hx = hiword(x), hy = hiword(y);
-    const int ix = hx & 0x7fffffff, iy = hy & 0x7fffffff;
-    const bool x_special = (ix | loword(x)) == 0 || ix >= 0x7ff00000;
-    const bool y_special = (iy | loword(y)) == 0 || iy >= 0x7ff00000;
-    const int k = (iy - ix) >> 20;
-    if (__builtin_expect(x_special || y_special || k > 60 || k < -60, 0)) return atan2_pp(y, x);
-    const double ay = fabs(y), ax = fabs(x);
+// atan2 of (|y|, |x|) for finite arguments, not both zero, by ONE division and no divergent interval
+// branches; the caller applies y's sign. The argument reduction of atan_pos is applied to (|y|, |x|)
+// directly — e.g. t = (|y| - |x|) / (|x| + |y|) instead of (q - 1) / (q + 1) with a rounded
+// q = |y| / |x| — with interval selection by comparisons of 16 |y| against 7, 11, 19, 39 times |x|.
+// Held under 1 ulp (tests/test_math_primitives.py; 0.75 measured), which fdlibm's form misses (1.18
+// ulp measured: the rounded 3 |x| and 3 |y| of the third interval, the rounded quotient, and a second
+// rounding in the quadrant step pi - (z - pi_lo)):
+// - numerator and denominator round once at most (the differences are exact by Sterbenz, the third
+//   interval's two by one fma each), and the quotient is corrected by ct = rt / den from the
+//   division's exact residual rt = num - t den, a term below half an ulp of t for which the 24-bit
+//   v_rcp_f64 is plenty: where the result falls into the binade below t's, half an ulp of t is a
+//   whole ulp of it (ct is zero when rt is — subnormal operands — so that an infinite reciprocal
+//   cannot make a NaN, and dropped if an overflowing denominator made it non-finite);
+// - the quadrant is folded into the interval constant: the result is A + (ts - (ts p - (B + cts)))
+//   with (A, B) = atan(c) for x > 0 and pi - atan(c) for x < 0 as double-doubles (kAtanAB), ts, cts =
+//   +-t, +-ct, and p the polynomial; one rounding of a small term, then the final one.
+// Zero and tiny or huge ratios go through the same steps: t = +-0 gives +0 or A + B rounded (pi/2,
+// pi), the values atan2_pp returns for a zero argument; a tiny t the rounded quotient or the
+// correctly rounded A + B -+ t (where atan2_pp's short cuts for exponent gaps beyond 60 are up to
+// 0.72 ulp off); NaN propagates.
+// (A, B) per-lane table loads: the branch is rare, and constants selected in registers would be
+// hoisted out of the candidate loop and held there.
+__constant__ double kAtanAB[20] = {
+    0.0, 0.0,                                                      // x > 0: atan(0), atan(1/2), pi/4,
+    4.63647609000806093515e-01, 2.26987774529616870924e-17,        //        atan(3/2), pi/2
+    7.85398163397448278999e-01, 3.06161699786838301793e-17,
+    9.82793723247329054082e-01, 1.39033110312309984516e-17,
+    1.57079632679489655800e+00, 6.12323399573676603587e-17,
+    3.14159265358979311600e+00, 1.22464679914735320717e-16,        // x < 0: pi minus those
+    2.67794504458898696697e+00, 1.55277053693031466809e-16,
+    2.35619449019234483700e+00, 9.18485099360514843751e-17,
+    2.15879893034246395089e+00, 2.19583671346019967064e-16,
+    1.57079632679489655800e+00, 6.12323399573676603587e-17};
+__device__ __forceinline__ double atan2_core(double ay, double ax, bool xneg) {
     const double y16 = 16.0 * ay;
     // interval id: -1 (q < 7/16), 0 (< 11/16), 1 (< 19/16), 2 (< 39/16), 3 (>= 39/16)
     const int id = (y16 < 7.0 * ax) ? -1 : (y16 < 11.0 * ax) ? 0 : (y16 < 19.0 * ax) ? 1
                  : (y16 < 39.0 * ax) ? 2 : 3;
     // t = num / den per interval (fdlibm's reductions multiplied through by |x|)
-    double num, den, hi, lo;
-    if (id < 0)       { num = ay;                  den = ax;                  hi = 0.0; lo = 0.0; }
-    else if (id == 0) { num = 2.0 * ay - ax;       den = 2.0 * ax + ay;
-                        hi = 4.63647609000806093515e-01; lo = 2.26987774529616870924e-17; }
-    else if (id == 1) { num = ay - ax;             den = ax + ay;
-                        hi = 7.85398163397448278999e-01; lo = 3.06161699786838301793e-17; }
-    else if (id == 2) { num = 2.0 * ay - 3.0 * ax; den = 2.0 * ax + 3.0 * ay;
-                        hi = 9.82793723247329054082e-01; lo = 1.39033110312309984516e-17; }
-    else              { num = -ax;                 den = ay;
-                        hi = 1.57079632679489655800e+00; lo = 6.12323399573676603587e-17; }
+    double num, den;
+    if (id < 0)       { num = ay;                                  den = ax; }
+    else if (id == 0) { num = 2.0 * ay - ax;                       den = 2.0 * ax + ay; }
+    else if (id == 1) { num = ay - ax;                             den = ax + ay; }
+    else if (id == 2) { num = __builtin_fma(-3.0, ax, 2.0 * ay);   den = __builtin_fma(3.0, ay, 2.0 * ax); }
+    else              { num = -ax;                                 den = ay; }
     const double t = num / den;
+    const double rt = __builtin_fma(-t, den, num);
+    double ct = rt == 0.0 ? 0.0 : rt * __builtin_amdgcn_rcp(den);
+    ct = fabs(ct) <= 0x1p-50 ? ct : 0.0;
+    const double A = kAtanAB[10 * (int)xneg + 2 * (id + 1)], B = kAtanAB[10 * (int)xneg + 2 * (id + 1) + 1];
     const double aT0 = 3.33333333333329318027e-01, aT1 = -1.99999999998764832476e-01,
                  aT2 = 1.42857142725034663711e-01, aT3 = -1.11111104054623557880e-01,
                  aT4 = 9.09088713343650656196e-02, aT5 = -7.69187620504482999495e-02,
@@ -243,53 +267,29 @@ __device__ __forceinline__ double atan2_fast(double y, double x) {
     const double w = z * z;
     const double s1 = z * (aT0 + w * (aT2 + w * (aT4 + w * (aT6 + w * (aT8 + w * aT10)))));
     const double s2 = w * (aT1 + w * (aT3 + w * (aT5 + w * (aT7 + w * aT9))));
-    const double zz = (id < 0) ? t - t * (s1 + s2) : hi - ((t * (s1 + s2) - lo) - t);
-    const int m = ((hy >> 31) & 1) | ((hx >> 30) & 2);  // 2*sign(x) + sign(y)
-    return m == 0 ? zz : m == 1 ? -zz : m == 2 ? pi - (zz - pi_lo) : (zz - pi_lo) - pi;
+    const double ts = xneg ? -t : t, cts = xneg ? -ct : ct;
+    return A + (ts - __builtin_fma(ts, s1 + s2, -(B + cts)));
+}
+
+// atan2(y, x) for finite nonzero arguments by atan2_core; zero and non-finite arguments take
+// atan2_pp (the C standard's special values)
+__device__ __forceinline__ double atan2_fast(double y, double x) {
+    const int hx = hiword(x), hy = hiword(y);
+    const int ix = hx & 0x7fffffff, iy = hy & 0x7fffffff;
+    const bool x_special = (ix | loword(x)) == 0 || ix >= 0x7ff00000;
+    const bool y_special = (iy | loword(y)) == 0 || iy >= 0x7ff00000;
+    if (__builtin_expect(x_special || y_special, 0)) return atan2_pp(y, x);
+    const double r = atan2_core(fabs(y), fabs(x), hx < 0);
+    return hy < 0 ? -r : r;
 }
 
 // atan2_fast for finite (y, x) that are not both zero (the wide-turn branch of the candidate
-// loop: components of unit vectors): no special-case fallback. Zero, tiny (|y/x| < 2^-60) and huge
-// (> 2^60) ratios go through the same reduction: t = 0 or a tiny/huge-ratio t gives the values
-// atan2_pp returns for them (+-0, +-pi/2, +-pi: hi + lo and pi - (t - pi_lo) round to those
-// constants), NaN propagates. tools/atan2_check.hip compares the two on the GPU.
-// atan_pos's interval constants (hi, lo) for id = -1 .. 3 (atan2_unit)
-__constant__ double kAtanHiLo[10] = {
-    0.0, 0.0,
-    4.63647609000806093515e-01, 2.26987774529616870924e-17,
-    7.85398163397448278999e-01, 3.06161699786838301793e-17,
-    9.82793723247329054082e-01, 1.39033110312309984516e-17,
-    1.57079632679489655800e+00, 6.12323399573676603587e-17};
+// loop: components of unit vectors): no special-case fallback, the same bits (atan2_core's zero and
+// tiny-ratio cases; tools/atan2_check.hip and tests/test_math_primitives.py compare the two on the
+// GPU). x = -0 counts as +0 (atan2(y, -0) = +-pi/2).
 __device__ __forceinline__ double atan2_unit(double y, double x) {
-    const double pi = 3.1415926535897931160E+00, pi_lo = 1.2246467991473531772E-16;
-    const int hy = hiword(y);
-    const double ay = fabs(y), ax = fabs(x);
-    const double y16 = 16.0 * ay;
-    const int id = (y16 < 7.0 * ax) ? -1 : (y16 < 11.0 * ax) ? 0 : (y16 < 19.0 * ax) ? 1
-                 : (y16 < 39.0 * ax) ? 2 : 3;
-    double num, den;
-    if (id < 0)       { num = ay;                  den = ax; }
-    else if (id == 0) { num = 2.0 * ay - ax;       den = 2.0 * ax + ay; }
-    else if (id == 1) { num = ay - ax;             den = ax + ay; }
-    else if (id == 2) { num = 2.0 * ay - 3.0 * ax; den = 2.0 * ax + 3.0 * ay; }
-    else              { num = -ax;                 den = ay; }
-    // the interval constants by a per-lane table load: the branch is rare, and constants
-    // selected in registers would be hoisted out of the candidate loop and held there
-    const double hi = kAtanHiLo[2 * (id + 1)], lo = kAtanHiLo[2 * (id + 1) + 1];
-    const double t = num / den;
-    const double aT0 = 3.33333333333329318027e-01, aT1 = -1.99999999998764832476e-01,
-                 aT2 = 1.42857142725034663711e-01, aT3 = -1.11111104054623557880e-01,
-                 aT4 = 9.09088713343650656196e-02, aT5 = -7.69187620504482999495e-02,
-                 aT6 = 6.66107313738753120669e-02, aT7 = -5.83357013379057348645e-02,
-                 aT8 = 4.97687799461593236017e-02, aT9 = -3.65315727442169155270e-02,
-                 aT10 = 1.62858201153657823623e-02;
-    const double z = t * t;
-    const double w = z * z;
-    const double s1 = z * (aT0 + w * (aT2 + w * (aT4 + w * (aT6 + w * (aT8 + w * aT10)))));
-    const double s2 = w * (aT1 + w * (aT3 + w * (aT5 + w * (aT7 + w * aT9))));
-    const double zz = (id < 0) ? t - t * (s1 + s2) : hi - ((t * (s1 + s2) - lo) - t);
-    const int m = ((hy >> 31) & 1) | (x < 0.0 ? 2 : 0);   // x = -0 counts as +0 (atan2(y, -0) = +-pi/2)
-    return m == 0 ? zz : m == 1 ? -zz : m == 2 ? pi - (zz - pi_lo) : (zz - pi_lo) - pi;
+    const double r = atan2_core(fabs(y), fabs(x), x < 0.0);
+    return hiword(y) < 0 ? -r : r;
 }
 
 // Angle between consecutive step directions without atan2 (run_candidate). The reference turns
@@ -325,14 +325,18 @@ __device__ __forceinline__ double rcp_nr(double d) {
 // n / d from r ~ 1/d (within ~1 ulp): q0 = n r, then one Markstein correction with the exact
 // residual n - q0 d (fma). With r within half an ulp of 1/d (r = RN(1/d), e.g. 0.02 for 50) the
 // result is the correctly rounded quotient; with rcp_nr's r it is in all but rare cases (then one
-// ulp away). Zero and non-finite operands, and |d| or |n| outside [2^-900, 2^900] (where the
-// residual could underflow), take the IEEE division.
+// ulp away). Zero and non-finite operands, |d| or |n| outside [2^-900, 2^900] (where the
+// residual could underflow), and a result outside [2^-1021, 2^1023] take the IEEE division: a
+// quotient that overflows makes q0 infinite and the correction inf - inf = NaN where IEEE gives the
+// infinity, and below 2^-1021 q0 may be subnormal, no longer within an ulp of the quotient (the
+// comparisons are false for a NaN result too). tests/test_math_primitives.py holds all of this.
 __device__ __forceinline__ double div_rcp(double n, double d, double r) {
     const double q0 = n * r;
     const double e = __builtin_fma(-q0, d, n);
     const double q = __builtin_fma(e, r, q0);
-    const double ad = fabs(d), an = fabs(n);
-    const bool ok = ad >= 0x1p-900 && ad <= 0x1p900 && (an == 0.0 || (an >= 0x1p-900 && an <= 0x1p900));
+    const double ad = fabs(d), an = fabs(n), aq = fabs(q);
+    const bool ok = ad >= 0x1p-900 && ad <= 0x1p900 &&
+                    (an == 0.0 || (an >= 0x1p-900 && an <= 0x1p900 && aq >= 0x1p-1021 && aq <= 0x1p1023));
     if (__builtin_expect(!ok, 0)) return n / d;
     return an == 0.0 ? q0 : q;        // +-0 / d: q0 carries the quotient's sign
 }
@@ -355,13 +359,15 @@ __device__ __forceinline__ double div50_nc(double v) {
 }
 
 // n / d with r ~ 1/d for a d known to lie in [2^-450, 2^450] (dok: sqrt_rd's fast path);
-// otherwise, and for |n| outside [2^-900, 2^900], the IEEE division
+// otherwise, for |n| outside [2^-900, 2^900] and for a result outside [2^-1021, 2^1023] (an
+// overflowing or subnormal quotient, as in div_rcp), the IEEE division
 __device__ __forceinline__ double div_rcp_n(double n, double d, double r, bool dok) {
     const double q0 = n * r;
     const double e = __builtin_fma(-q0, d, n);
     const double q = __builtin_fma(e, r, q0);
-    const double an = fabs(n);
-    if (__builtin_expect(!(dok && an >= 0x1p-900 && an <= 0x1p900), 0)) return (dok && an == 0.0) ? q0 : n / d;
+    const double an = fabs(n), aq = fabs(q);
+    if (__builtin_expect(!(dok && an >= 0x1p-900 && an <= 0x1p900 && aq >= 0x1p-1021 && aq <= 0x1p1023), 0))
+        return (dok && an == 0.0) ? q0 : n / d;
     return q;
 }
 

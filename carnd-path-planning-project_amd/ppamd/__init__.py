@@ -194,7 +194,7 @@ EXPORTS = ["pp_params_default", "pp_num_candidates", "pp_version", "pp_map_creat
            "pp_num_lanes", "pp_max_cars", "pp_libm_eval", "pp_debug_set", "pp_debug_get",
            "pp_judge_cfg_default", "pp_judge_frame", "pp_judge_frame_host", "pp_rollout_judged",
            "pp_follow_cfg_default", "pp_traffic_follow", "pp_traffic_follow_host", "pp_rollout_reactive",
-           "pp_episode_cfg_default", "pp_synth_episode", "pp_synth_episode_host"]
+           "pp_episode_cfg_default", "pp_synth_episode", "pp_synth_episode_host", "pp_math_eval"]
 
 
 def _load():
@@ -306,6 +306,8 @@ def _load():
     lib.pp_control_format_device.restype = C.c_int32
     lib.pp_libm_eval.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
     lib.pp_libm_eval.restype = C.c_int32
+    lib.pp_math_eval.argtypes = [C.c_int32] + [C.c_void_p] * 7 + [C.c_int64, C.c_int32, C.c_void_p]
+    lib.pp_math_eval.restype = C.c_int32
     return lib
 
 
@@ -894,6 +896,42 @@ def libm_eval(kind, a, b=None, device=None):
     st = torch.cuda.current_stream(device).cuda_stream
     _check(lib.pp_libm_eval(k, a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), device, st), "pp_libm_eval")
     return out
+
+
+# include/pp.h PP_MATH_*: kind -> (number, inputs, outputs)
+MATH_KINDS = {name: (i, nin, nout) for i, (name, nin, nout) in enumerate([
+    ("sincos", 1, 2), ("sincos_nolarge", 1, 2), ("atan2_pp", 2, 1), ("atan2_fast", 2, 1), ("atan2_unit", 2, 1),
+    ("asin_small", 1, 1), ("rcp_nr", 1, 1), ("div_rcp", 3, 1), ("div_rcp_nc", 3, 1), ("div_rcp_auto", 2, 1),
+    ("div_rcp_nc_auto", 2, 1), ("div50", 1, 1), ("div50_nc", 1, 1), ("sqrt_rd", 1, 3), ("div_rcp_n", 2, 1),
+    ("div_rcp_d", 2, 1), ("fmod_2pi", 1, 1), ("fmod_2pi_small", 1, 1), ("turn_sincos", 1, 2),
+    ("turn_sincos_nolarge", 1, 2), ("sincos_small", 1, 2), ("turn_angle", 3, 1), ("turn_angle_nolarge", 3, 1),
+    ("turn_angle_fast", 3, 1), ("sc_speed", 4, 1), ("sc_speed_r", 4, 1), ("sc_speed_r_nc", 4, 1),
+    ("sc_override", 4, 1), ("sc_override_r", 4, 1), ("sc_override_r_nc", 4, 1), ("speed_in_range", 1, 1)])}
+
+
+def math_eval(kind, a, b=None, c=None, d=None, device=0):
+    """pp_math_eval: one of the candidate loop's FP64 primitives (csrc/pp_math.h and its wrappers)
+    over float64 torch tensors on `device`; returns the tuple of the kind's outputs, each of a's
+    shape. For the sc_* kinds d is [2, n] (shift, step count k; t = 0.02 k) or, for sc_override*,
+    [3, n] (shift, k, speed)."""
+    import torch
+    k, nin, nout = MATH_KINDS[kind]
+    ins = [a, b, c, d]
+    if any(x is None for x in ins[:nin]):
+        raise ValueError(f"math_eval({kind}) takes {nin} inputs")
+    ins = [x.contiguous() if x is not None else None for x in ins]
+    n = ins[0].numel()
+    dplanes = 3 if kind.startswith("sc_override") else 2
+    for j, x in enumerate(ins[:nin]):
+        planes = dplanes if j == 3 else 1
+        if x.dtype != torch.float64 or not x.is_cuda or x.numel() != planes * n:
+            raise ValueError(f"math_eval({kind}): input {j} must be a float64 device tensor of {planes} x {n}")
+    outs = [torch.empty_like(ins[0]) for _ in range(nout)]
+    st = torch.cuda.current_stream(device).cuda_stream
+    p = [x.data_ptr() if x is not None else None for x in ins[:nin]] + [None] * (4 - nin)
+    o = [x.data_ptr() for x in outs] + [None] * (3 - nout)
+    _check(lib.pp_math_eval(k, *p, *o, n, device, st), "pp_math_eval")
+    return tuple(outs)
 
 
 # ---- wire codec (include/pp.h pp_telemetry_parse / pp_control_format; host) ----------------------

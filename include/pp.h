@@ -632,6 +632,45 @@ double  pp_mc_gauss(uint64_t seed, int64_t scene, int32_t draw, int32_t car, int
 int32_t pp_libm_eval(int32_t kind, const double* a, const double* b, double* out, int64_t n,
                      int32_t device, void* hip_stream);
 
+/* The candidate loop's FP64 primitives over arrays (csrc/pp_math.h, the SpeedController wrappers of
+ * csrc/pp_device.h, the turn functions of csrc/pp_k_frame.h), each kind calling the function the
+ * loop calls: for tests/test_math_primitives.py, which holds every primitive's written accuracy
+ * claim against an exact reference. Every pointer is device memory on `device` (>= 0), work goes
+ * to `hip_stream`; inputs and outputs a kind does not use are null; booleans pass as 0.0 / 1.0.
+ *   kind                                  in                          out
+ *   SINCOS, SINCOS_NOLARGE                a                           sin, cos   (sincos_pp<true/false>)
+ *   ATAN2_PP, ATAN2_FAST, ATAN2_UNIT      a = y, b = x                angle
+ *   ASIN_SMALL, RCP_NR                    a                           value
+ *   DIV_RCP, DIV_RCP_NC                   a = n, b = d, c = r         quotient
+ *   DIV_RCP_AUTO, DIV_RCP_NC_AUTO         a = n, b = d                quotient   (r = rcp_nr(d) inside)
+ *   DIV50, DIV50_NC                       a                           div_rcp(a, 50, 0.02), div50_nc(a)
+ *   SQRT_RD                               a                           d, rd, dok
+ *   DIV_RCP_N, DIV_RCP_D                  a = n, b = q                n / sqrt(q)  (sqrt_rd(q) first)
+ *   FMOD_2PI, FMOD_2PI_SMALL              a                           remainder
+ *   TURN_SINCOS, TURN_SINCOS_NOLARGE      a                           sin, cos   (turn_sincos<true/false>)
+ *   SINCOS_SMALL                          a                           sin, cos
+ *   TURN_ANGLE, _NOLARGE, _FAST           a = nc, b = speed, c = adiff  rot      (turn_angle<true/false>, turn_angle_fast)
+ *   SC_SPEED, SC_SPEED_R, SC_SPEED_R_NC   a, b, c = start, target, ttime; d = 2 planes of n: shift, k
+ *                                         speed at t = 0.02 k (sc_get_speed; sc_get_speed_r<true/false>
+ *                                         with r = rcp_nr(ttime))
+ *   SC_OVERRIDE, _R, _R_NC                a, b, c as above; d = 3 planes of n: shift, k, speed
+ *                                         the new shift (sc_override; sc_override_r<true/false> with
+ *                                         r = rcp_nr(target - start))
+ *   SPEED_IN_RANGE                        a                           0 / 1
+ * A bad kind, a missing array, n < 0 or a bad device: PP_ERR_ARG; n = 0: PP_OK. */
+enum {
+    PP_MATH_SINCOS = 0, PP_MATH_SINCOS_NOLARGE, PP_MATH_ATAN2_PP, PP_MATH_ATAN2_FAST, PP_MATH_ATAN2_UNIT,
+    PP_MATH_ASIN_SMALL, PP_MATH_RCP_NR, PP_MATH_DIV_RCP, PP_MATH_DIV_RCP_NC, PP_MATH_DIV_RCP_AUTO,
+    PP_MATH_DIV_RCP_NC_AUTO, PP_MATH_DIV50, PP_MATH_DIV50_NC, PP_MATH_SQRT_RD, PP_MATH_DIV_RCP_N,
+    PP_MATH_DIV_RCP_D, PP_MATH_FMOD_2PI, PP_MATH_FMOD_2PI_SMALL, PP_MATH_TURN_SINCOS,
+    PP_MATH_TURN_SINCOS_NOLARGE, PP_MATH_SINCOS_SMALL, PP_MATH_TURN_ANGLE, PP_MATH_TURN_ANGLE_NOLARGE,
+    PP_MATH_TURN_ANGLE_FAST, PP_MATH_SC_SPEED, PP_MATH_SC_SPEED_R, PP_MATH_SC_SPEED_R_NC,
+    PP_MATH_SC_OVERRIDE, PP_MATH_SC_OVERRIDE_R, PP_MATH_SC_OVERRIDE_R_NC, PP_MATH_SPEED_IN_RANGE,
+    PP_MATH_KINDS
+};
+int32_t pp_math_eval(int32_t kind, const double* a, const double* b, const double* c, const double* d,
+                     double* out0, double* out1, double* out2, int64_t n, int32_t device, void* hip_stream);
+
 /* Library version / build info string. */
 const char* pp_version(void);
 

@@ -3,11 +3,13 @@
 // vectors over every direction, random pairs over many binades, and the edge cases (signed zeros,
 // |y/x| beyond 2^+-60, subnormals, the interval boundaries 7/16, 11/16, 19/16, 39/16).
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -I../carnd-path-planning-project_amd/csrc
-// Exit status 0 iff every input agrees.
+// Usage: atan2_check [nu]: nu inputs in each of the two large random sections and nu / 4 near the
+// interval boundaries (default 2^24). Exit status 0 iff every input agrees.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 #include "pp_math.h"
 
@@ -27,7 +29,7 @@ static uint64_t rng = 0x9E3779B97F4A7C15ull;
 static uint64_t next() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return rng; }
 static double uni() { return (next() >> 11) * 0x1p-53; }
 
-int main() {
+int main(int argc, char** argv) {
     std::vector<double> ys, xs;
     const double specials[] = {0.0, -0.0, 1.0, -1.0, 0x1p-61, -0x1p-61, 0x1p-70, 5e-324, -5e-324,
                                1e-300, 0x1p-1022, 7.0 / 16, 11.0 / 16, 19.0 / 16, 39.0 / 16, 0.5,
@@ -39,7 +41,12 @@ int main() {
             for (int sa = -1; sa <= 1; sa += 2)
                 for (int sb = -1; sb <= 1; sb += 2) { ys.push_back(sa * a); xs.push_back(sb * b); }
         }
-    const int nu = 1 << 24;
+    int nu = 1 << 24;
+    if (argc > 1) {
+        const long v = atol(argv[1]);
+        if (v < 4 || v > (1 << 24)) { fprintf(stderr, "nu must be in [4, 2^24]\n"); return 2; }
+        nu = (int)v;
+    }
     for (int i = 0; i < nu; i++) {                 // unit vectors (the loop's inputs)
         const double t = (uni() * 2 - 1) * M_PI;
         ys.push_back(std::sin(t)); xs.push_back(std::cos(t));
