@@ -93,6 +93,9 @@ constexpr int kSplitMax = 4;
 // parts per call: a batch beyond kSplitMaxScenes runs as chunks of parts, part t on stream t % streams
 // (split_chunks); each part has its own flagged-group count word and 4 timing-event slots
 constexpr int kPartMax = 16;
+// the persistent kernels' claim counters, behind the parts' count words (zeroed with them, on the
+// stream, ahead of every call's K1): word 0 the persistent k_cand's
+constexpr int kPersistCtr = 2;
 struct StreamWS {
     DevMem<> ws;                  // prep workspace (capacity: evaluations, scene x draw)
     DevMem<> rec;                 // reference-mode winner record (capacity: scenes)
@@ -130,6 +133,10 @@ struct DevState : DevRes {
     std::mutex stage_mu;          // one pp_plan_batch_host at a time per device
     pptab::CarTable plan_table;   // pp_plan_frame's persistent car table (the reference's std::map)
     int timing = 0;               // pp_timing_enable: 0 off, 1 every kernel, 2 K2 only
+    // the persistent k_cand's resident blocks on this device (occupancy query x CUs), asked once
+    // per launch geometry (threads, LDS bytes); 0: not asked yet
+    int persist_blocks = 0, persist_threads = 0;
+    size_t persist_lds = 0;
 };
 
 }  // namespace

@@ -497,7 +497,11 @@ __device__ __forceinline__ void cand_store_slot(const CandSm& L, int nslot, doub
 // single-frame and small-batch step, whose time is the winners' serial chain)
 // kPreA: the block's (single) scene has its fast-path spline slots built already (k_plan_frame's
 // second wave builds them while the first runs K1): phase A is skipped
-template <bool kSlow, int kMode, int kEmitIn = 0, bool kPreA = false>
+// kLoop: the caller runs group after group in one block (the persistent k_cand): the thread index
+// is taken through an empty asm statement, so the compiler computes the per-thread set-up where
+// each group uses it, as in the one-group kernels, and does not carry it in registers across the
+// candidate loop (hoisted out of the caller's loop it spills there)
+template <bool kSlow, int kMode, int kEmitIn = 0, bool kPreA = false, bool kLoop = false>
 __device__ __forceinline__ void cand_group(const MapG& mg, const pp_scene_batch& in, const pp_params& P,
                                            const PrepV& pv, const pp_result& out, int SPB, int BPS,
                                            double* rec, uint64_t* adjm, int64_t g, double* sm,
@@ -536,7 +540,8 @@ __device__ __forceinline__ void cand_group(const MapG& mg, const pp_scene_batch&
     } else {
         nsc = (int)((S - s0) < SPB ? (S - s0) : SPB);
     }
-    const int tid = threadIdx.x;
+    int tid = threadIdx.x;
+    if (kLoop) asm volatile("" : "+v"(tid));
     // per scene: any of its draws flagged kLimSlow (absurd heading, or a speed or ramp time outside
     // the range of the unchecked divisions) -> the scene runs in the k_cand<true> instantiation
     uint32_t* sSlow = sFlags + SPB;
@@ -564,7 +569,10 @@ __device__ __forceinline__ void cand_group(const MapG& mg, const pp_scene_batch&
         const int q = t / D;
         if (pv.lim_mask[(s0 + q) * D + (t - q * D)] & kLimSlow) { atomicOr(&sSlow[q], 1u); mine = true; }
     }
-    if (!__syncthreads_or(mine) && kSlow) return;      // whole block leaves: no flagged scene
+    // (kLoop is k_cand<false>'s: the vote's result is not used there, only its barrier; the vote's
+    // flat thread index would otherwise stay in registers from group to group)
+    if (kLoop && !kSlow) __syncthreads();
+    else if (!__syncthreads_or(mine) && kSlow) return;      // whole block leaves: no flagged scene
     if (!kPreA) {   // phase A: a team of TS threads per slot (team_a1..a5), block barriers between the steps
         int TS = (int)blockDim.x / nslot;
         if (TS > 8) TS = 8;
@@ -797,5 +805,44 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kCandWaves)
         __syncthreads();                                          // the previous group's LDS readers are done
         cand_group<true, kMode>(mg, in, P, pv, out, SPB, BPS, rec, adjm, g, sm, wslot);
         if (threadIdx.x == 0) atomicAnd(&gbits[g >> 5], ~(1u << (g & 31)));
+    }
+}
+
+// The persistent fast path of reference mode (kMode 1 without paths or draws, large batches on one
+// stream): the grid is the device's resident block count; block b runs group b, then the groups it
+// claims from `next` (a counter of the stream's workspace that pp_eval zeroes ahead of K1: claim i
+// is group gridDim.x + i), so a block's slot never waits for the dispatcher between two groups and
+// the spread of the groups' times (53-81 us) is absorbed by the order of the claims. One thread
+// claims; the group index reaches the block through the word behind the block's LDS
+// (CandLds::bytes_persist), and the barrier of that broadcast is also the one that separates the
+// previous group's LDS readers from the next group's writers. A block beyond the batch's groups
+// leaves before it touches LDS. The groups themselves are cand_group<false, kMode>'s, bit for bit;
+// flagged scenes are left to k_cand<true>, launched after this kernel as after k_cand<false>.
+struct Persist {};
+// its arguments, one struct at offset 0 of the kernel-argument segment: each group reads what it
+// needs from there through a pointer the compiler cannot follow across groups (scalar loads, as the
+// one-group kernels issue them), because arguments held in scalar registers across the candidate
+// loop overflow the scalar file into vector registers and those into scratch
+struct PersistArgs {
+    MapG mg; pp_scene_batch in; pp_params P; PrepV pv; pp_result out;
+    int SPB; double* rec; uint64_t* adjm; int64_t ngroups; uint32_t* next;
+};
+template <class kTag, int kMode>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kCandWaves))) void k_cand(PersistArgs a0) {
+    static_assert(kMode == 1, "the persistent K2 is reference mode's");
+    typedef const __attribute__((address_space(4))) PersistArgs* KArg;
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    int64_t g = blockIdx.x;
+    if (g >= a0.ngroups) return;
+    for (;;) {
+        KArg ka = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        const PersistArgs& a = *(const PersistArgs*)ka;
+        cand_group<false, kMode, 0, false, true>(a.mg, a.in, a.P, a.pv, a.out, a.SPB, 1, a.rec, a.adjm, g, sm, nullptr);
+        uint32_t* sNext = (uint32_t*)(sm + CandLds{a.SPB}.doubles());
+        if (threadIdx.x == 0) *sNext = atomicAdd(a.next, 1u);
+        __syncthreads();
+        g = (int64_t)gridDim.x + *sNext;
+        if (g >= a.ngroups) return;
     }
 }

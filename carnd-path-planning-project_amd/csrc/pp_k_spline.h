@@ -61,7 +61,11 @@ struct CandLds {
     // K4 inside k_cand: once phase B is done the winners' sin/cos tables (N doubles each, two per
     // scene) overlay the slot area, so they have to fit it
     __host__ __device__ constexpr bool replay_fits(int N) const { return 2 * spb * N <= slot_doubles(); }
+    // the persistent k_cand: one more word at doubles(), the group the block claimed
+    __host__ __device__ constexpr size_t bytes_persist() const { return sizeof(double) * (size_t)doubles() + 8; }
 };
+// the persistent k_cand keeps four blocks on a CU (160 KB of LDS) at config 5's 17 scenes per block
+static_assert(PP_NUM_LANES != 3 || 4 * CandLds{17}.bytes_persist() <= 160 * 1024, "four persistent k_cand blocks per CU");
 #if PP_NUM_LANES == 3
 static_assert(CandLds{1}.bytes() == 2116 && CandLds{4}.bytes() == 8464 && CandLds{16}.bytes() == 33856, "k_cand's LDS");
 static_assert(CandLds{1}.bytes_cost() == 4168 && CandLds{4}.bytes_cost() == 10512 &&

@@ -80,6 +80,19 @@ int split_chunks(int64_t S) {
     const int64_t c = (S + kChunkScenes - 1) / kChunkScenes;
     return (int)std::min<int64_t>(c, kPartMax / kSplitMax);
 }
+// The persistent K2 (k_cand<Persist, 1>: reference mode without paths or draws, one stream): the
+// batches beyond the split's range, where the grid is ~120 rounds of blocks and the dispatcher's
+// refill of a block slot (~5 us after a ~64 us block) is what the step still pays beside its
+// arithmetic (2,097,152 scenes: step 9.73-9.85 -> 9.47-9.60 ms, k_cand 7.29-7.33 -> 7.01-7.03).
+// Measured against the split (profiles/persist_ablations.txt): slower at 262,144 and 524,288
+// scenes (+1.3 / +1.0 %), level at 1,048,576, 2.5 % faster at 1,572,864, so the split keeps its
+// range. PP_DBG_PERSIST 1 forces it for every batch launch_plain runs with the k_cand pair, 2
+// turns it off; the last call's resident block count is read back with PP_DBG_LAST_PERSIST.
+constexpr int64_t kPersistMinScenes = kSplitMaxScenes + 1;
+bool persist_on(int64_t S) {
+    const int f = dbg(PP_DBG_PERSIST);
+    return f == 1 || (f == 0 && S >= kPersistMinScenes);
+}
 // K1 (one lane per evaluation): 3 waves per SIMD, or 4 where the batch's waves fill whole rounds of
 // 4 better. Round 5 (the approach table in the 3-wave build's LDS): a round of 3 waves per SIMD
 // takes ~0.150 ms (config 5: 1.65 ms for 32,768 waves = 11 rounds), one of 4 ~0.357 ms (spills,
@@ -176,8 +189,9 @@ int ensure_gbits(StreamWS& W, hipStream_t st, int64_t ngroups) {
     const int64_t words = (ngroups + 31) / 32;
     if (W.gbits.cap() >= words) return PP_OK;
     const int64_t cap = std::max<int64_t>(words, 1024);
-    // [bits: cap words][the parts' flagged-group counts: kPartMax words][list: 32 cap entries]
-    const size_t bytes = sizeof(uint32_t) * (size_t)(cap + kPartMax + 32 * cap);
+    // [bits: cap words][the parts' flagged-group counts: kPartMax words][the persistent kernels'
+    // claim counters: kPersistCtr words][list: 32 cap entries]
+    const size_t bytes = sizeof(uint32_t) * (size_t)(cap + kPartMax + kPersistCtr + 32 * cap);
     DevMem<uint32_t> g = std::move(W.gbits);       // (back only once it is cleared)
     const int rc = g.grow(st, cap, bytes);
     if (rc) return rc;
@@ -285,6 +299,7 @@ struct EvalPlan {
     // most 16 rows per scene (k_prep's own sorting rule; larger tables keep the identity order)
     bool need_srt;
     bool split;               // the multi-stream split (split_on)
+    bool persist;             // the persistent K2 in place of k_cand<false> (persist_on)
 };
 int32_t eval_plan(const pp_map* M, const pp_scene_batch* in, const pp_params* prm, int32_t device, EvalPlan& p) {
     p.S = in->n_scenes;
@@ -312,6 +327,8 @@ int32_t eval_plan(const pp_map* M, const pp_scene_batch* in, const pp_params* pr
                  in->car_stride <= 16 && p.prep_g == 1;
     p.split = p.ref_direct && !prm->emit_paths && !p.fused && p.cg.bps == 1 && p.Dn == 1 && p.prep_g == 1 &&
               split_on(p.S);
+    p.persist = p.ref_direct && !prm->emit_paths && !p.fused && !p.split && p.cg.bps == 1 && p.Dn == 1 &&
+                persist_on(p.S);
     return PP_OK;
 }
 
@@ -330,6 +347,8 @@ struct EvalArgs {
     double* wslot = nullptr;  // the stored winner slots (null: not in use)
     size_t cand_lds;          // k_cand's dynamic LDS
     SortedCars srt = {};      // rows 0: not in use
+    uint32_t* next = nullptr; // the persistent kernels' claim counters (kPersistCtr words, zero before K1)
+    unsigned persist = 0;     // the persistent k_cand's blocks (0: the call takes k_cand<false>)
 };
 
 // the stream's workspace at the call's size, then every argument of the call's launches: A is
@@ -376,7 +395,8 @@ int32_t eval_bind(const pp_map* M, const DevState& DS, StreamWS& W, const pp_sce
     if (!A.P.emit_paths) { A.R.paths = nullptr; A.R.path_len = nullptr; }
     A.gb.bits = W.gbits.get(); A.gb.SPB = p.cg.spb; A.gb.BPS = p.cg.bps; A.gb.C = p.Cn;
     A.gb.count = W.gbits.get() + W.gbits.cap();
-    A.gb.list = A.gb.count + kPartMax;
+    A.next = A.gb.count + kPartMax;
+    A.gb.list = A.next + kPersistCtr;
     return PP_OK;
 }
 
@@ -397,7 +417,7 @@ int32_t poison_fill(const StreamWS& W, hipStream_t st, const EvalPlan& p, const 
     const bool ok = fill(W.ws.get(), prep_bytes(W.ws.cap())) &&
                     fill(W.rec.get(), W.rec ? rec_bytes(W.rec.cap()) : 0) &&
                     fill(W.srt.get(), (size_t)W.srt.cap()) &&
-                    fill(W.gbits.get() + W.gbits.cap() + kPartMax, sizeof(uint32_t) * 32 * (size_t)W.gbits.cap()) &&
+                    fill(W.gbits.get() + W.gbits.cap() + kPartMax + kPersistCtr, sizeof(uint32_t) * 32 * (size_t)W.gbits.cap()) &&
                     fill(out->winner, 4 * S) && fill(out->n_out, 4 * S) && fill(out->status, 4 * S) &&
                     fill(out->next_x, 8 * N * S) && fill(out->next_y, 8 * N * S) &&
                     fill(out->cost, 8 * Cn * S) && fill(out->info, sizeof(pp_scene_info) * S) &&
@@ -581,6 +601,24 @@ int32_t launch_split(const EvalArgs& A, const EvalPlan& p, const EvalEvents& E, 
     return PP_OK;
 }
 
+// the persistent k_cand's grid: the blocks of this launch geometry that the device holds at once
+// (the occupancy query, at most kCandWaves waves per SIMD, x CUs), asked once per device
+unsigned persist_blocks(DevState& DS, const CandGeom& cg, int device) {
+    const size_t lds = CandLds{cg.spb}.bytes_persist();
+    if (DS.persist_blocks == 0 || DS.persist_threads != cg.threads || DS.persist_lds != lds) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_cand<Persist, 1>, cg.threads, lds) != hipSuccess || nb < 1) {
+            (void)hipGetLastError();
+            nb = 1;
+        }
+        nb = std::min(nb, std::max(1, 4 * kCandWaves * 64 / cg.threads));
+        DS.persist_blocks = nb * cu_count(device);
+        DS.persist_threads = cg.threads;
+        DS.persist_lds = lds;
+    }
+    return (unsigned)DS.persist_blocks;
+}
+
 // One stream: K1 (after K0 where the rows are sorted), K2, then K4 or K3
 int32_t launch_plain(const EvalArgs& A, const EvalPlan& p, const EvalEvents& E) {
     hipStream_t st = A.st;
@@ -613,6 +651,15 @@ int32_t launch_plain(const EvalArgs& A, const EvalPlan& p, const EvalEvents& E) 
         else if (p.ref_direct && p.fused) {
             hipLaunchKernelGGL(k_cand_small, dim3(nb), dim3(cg.threads), cg.lds, st, A.mg, A.B, A.P, A.pv, A.R,
                                cg.spb, A.rec, A.adjm, A.gb.bits);
+        }
+        else if (p.ref_direct && A.persist) {
+            // resident blocks that claim their groups (at most one block per group), then the
+            // checked instantiation over the flagged groups as after k_cand<false>
+            const PersistArgs pa = {A.mg, A.B, A.P, A.pv, A.R, cg.spb, A.rec, A.adjm, cg.groups, A.next};
+            hipLaunchKernelGGL((k_cand<Persist, 1>), dim3(std::min(A.persist, nb)), dim3(cg.threads),
+                               CandLds{cg.spb}.bytes_persist(), st, pa);
+            hipLaunchKernelGGL((k_cand<true, 1>), dim3(nslow), dim3(cg.threads), A.cand_lds, st, A.mg, A.B, A.P, A.pv, A.R,
+                               cg.spb, cg.bps, A.rec, A.adjm, A.gb.bits, cg.groups, A.gb.list, A.gb.count, (int64_t)0, A.wslot);
         }
         else if (p.ref_direct) launch_cand<1>(A, st, cg, nb, nslow, A.gb.list, A.gb.count, 0);
         else launch_cand<0>(A, st, cg, nb, nslow, A.gb.list, A.gb.count, 0);
@@ -680,8 +727,11 @@ int32_t eval_impl(pp_map* M, const pp_scene_batch* in, const pp_params* prm, pp_
     rc = check_limits(W, p, A);
     if (rc) return rc;
 #endif
+    A.persist = p.persist && !p.step_fused ? persist_blocks(DS, p.cg, device) : 0;
+    g_dbg[PP_DBG_LAST_PERSIST].store((int)A.persist, std::memory_order_relaxed);
     if (p.step_fused) return launch_step(A, p, E, fio);
-    if (hipMemsetAsync(A.gb.count, 0, kPartMax * sizeof(uint32_t), A.st) != hipSuccess) return PP_ERR_HIP;
+    // (the parts' flagged-group counts and, behind them, the persistent kernels' claim counters)
+    if (hipMemsetAsync(A.gb.count, 0, (kPartMax + kPersistCtr) * sizeof(uint32_t), A.st) != hipSuccess) return PP_ERR_HIP;
     g_dbg[PP_DBG_LAST_PARTS].store(1, std::memory_order_relaxed);
     return p.split ? launch_split(A, p, E, W) : launch_plain(A, p, E);
 }

@@ -589,6 +589,11 @@ int32_t pp_ws_accept_key(const char* key, char* out, int32_t cap);
  *   PP_DBG_SORT_CARS   1: order each scene's cars in a pre-pass (k_sort_cars) so the one-lane K1
  *                      reads them visit-major (coalesced; same results, less fetched, slower),
  *                      2 or 0: K1 sorts and gathers them itself (the default)
+ *   PP_DBG_PERSIST     the persistent K2 of reference mode without paths or draws on one stream
+ *                      (resident blocks that claim their groups from a counter): 1 on for every
+ *                      such batch, 2 off (0: batches of more than 1,572,864 scenes)
+ *   PP_DBG_LAST_PERSIST read-only: the resident block count of the last pp_eval's persistent K2
+ *                      (its grid is that, or one block per group if fewer), 0 when it ran none
  * Returns PP_ERR_ARG for an unknown key or value. */
 #define PP_DBG_PREP_GROUP  0
 #define PP_DBG_PREP_WAVES  1
@@ -597,7 +602,9 @@ int32_t pp_ws_accept_key(const char* key, char* out, int32_t cap);
 #define PP_DBG_SPLIT       4
 #define PP_DBG_LAST_PARTS  5
 #define PP_DBG_SORT_CARS   6
-#define PP_DBG_KEYS        7
+#define PP_DBG_PERSIST     7
+#define PP_DBG_LAST_PERSIST 8
+#define PP_DBG_KEYS        9
 #define PP_SHAPE_SPLIT      1
 #define PP_SHAPE_CAND_SMALL 2
 #define PP_SHAPE_STEP       3
