@@ -19,6 +19,14 @@ void launch_follow(const ppsynth::LaneTables& T, const ppfollow::ArcTables& AT, 
                        tel->ego_y, tel->ego_speed_mph, tv, consume, *fc, *fs);
 }
 
+void launch_lane_change(const ppsynth::LaneTables& T, const ppfollow::ArcTables& AT, const pp_scene_batch* tel,
+                        const ppsynth::TrafficV& tv, int32_t consume, const pp_follow_cfg* fc, const pp_follow* fs,
+                        const pp_lane_change_cfg* lc, const pp_lane_change* ls, hipStream_t stream) {
+    const int64_t S = tel->n_scenes;
+    hipLaunchKernelGGL(k_lane_change, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, stream, T, AT, S, tel->ego_x,
+                       tel->ego_y, tel->ego_speed_mph, tv, consume, *fc, *fs, *lc, *ls);
+}
+
 // every argument check of pp_synth_episode and its host twin (no HIP call); *gap: the gap rule in force
 bool episode_ok(const pp_map* M, int64_t first_scene, const pp_episode_cfg* cfg, const pp_follow_cfg* gap_rule,
                 const pp_scene_batch* tel, const pp_traffic* traffic, const pp_judge* js, const pp_follow* fs,
@@ -45,12 +53,14 @@ bool episode_ok(const pp_map* M, int64_t first_scene, const pp_episode_cfg* cfg,
     return ppepisode::ring_ok(*cfg, *gap, min_loop);
 }
 
-// pp_rollout's loop; with follow state (fc, fs non-null) k_follow runs after pp_eval, with a judge (jc,
-// js non-null) k_judge runs before k_sim
+// pp_rollout's loop; with follow state (fc, fs non-null) k_follow runs after pp_eval, with lane-change
+// state (lc, ls non-null; needs the follow state) k_lane_change after k_follow, with a judge (jc, js
+// non-null) k_judge runs before k_sim
 int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
                      const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
                      void* hip_stream, const pp_judge_cfg* jc, const pp_judge* js,
-                     const pp_follow_cfg* fc = nullptr, const pp_follow* fs = nullptr) {
+                     const pp_follow_cfg* fc = nullptr, const pp_follow* fs = nullptr,
+                     const pp_lane_change_cfg* lc = nullptr, const pp_lane_change* ls = nullptr) {
     if (!M || !tel || !prm || !cfg || !res || device < 0 || device >= kMaxDev || !traffic_ok(traffic, tel))
         return PP_ERR_ARG;
     if (cfg->n_frames < 0 || cfg->consume < 1 || !(cfg->sensor_range >= 0) || prm->n_draws > 1 ||
@@ -85,6 +95,10 @@ int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const 
         if (rc != PP_OK) return rc;
         if (fs) {
             launch_follow(T, AT, tel, tv, cfg->consume, fc, fs, (hipStream_t)hip_stream);
+            if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
+        }
+        if (ls && tv.n > 0) {
+            launch_lane_change(T, AT, tel, tv, cfg->consume, fc, fs, lc, ls, (hipStream_t)hip_stream);
             if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
         }
         if (js) {
@@ -206,6 +220,71 @@ int32_t pp_traffic_follow(pp_map* M, const pp_scene_batch* tel, pp_traffic* traf
     launch_follow(T, AT, tel, traffic_view(traffic, tel->n_scenes), consume, cfg, state, (hipStream_t)hip_stream);
     if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
     return PP_OK;
+}
+
+void pp_lane_change_cfg_default(pp_lane_change_cfg* c) {
+    if (!c) return;
+    memset(c, 0, sizeof(*c));
+    c->politeness = 0.3;
+    c->threshold = 0.2;
+    c->right_bias = 0.0;
+    c->safe_brake = 3.0;
+    c->lateral_speed = 1.5;
+    c->ego_desired_speed = 22.2;
+    c->min_interval_steps = 250;
+}
+
+int32_t pp_traffic_lane_change(pp_map* M, const pp_scene_batch* tel, pp_traffic* traffic, int32_t consume,
+                               const pp_follow_cfg* fcfg, const pp_follow* fstate, const pp_lane_change_cfg* cfg,
+                               pp_lane_change* state, int32_t device, void* hip_stream) {
+    if (!M || device < 0 || device >= kMaxDev || !follow_ok(fcfg, fstate) || !lane_change_ok(cfg, state) ||
+        !follow_frame_ok(tel, traffic, consume))
+        return PP_ERR_ARG;
+    if (tel->n_scenes == 0 || traffic->n_cars == 0) return PP_OK;
+    DeviceGuard g(device);
+    ppsynth::LaneTables T;
+    ppfollow::ArcTables AT;
+    {
+        std::lock_guard<std::mutex> lk(M->mu);
+        int rc = dev_init(M, device);
+        if (rc) return rc;
+        rc = arc_init(M, device);
+        if (rc) return rc;
+        T = lane_tables(M->dev[device].tab.lanetab.get(), M->n);
+        AT = ppfollow::arc_tables(M->dev[device].arctab.get(), M->n);
+    }
+    launch_lane_change(T, AT, tel, traffic_view(traffic, tel->n_scenes), consume, fcfg, fstate, cfg, state,
+                       (hipStream_t)hip_stream);
+    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
+    return PP_OK;
+}
+
+int32_t pp_traffic_lane_change_host(const pp_map* M, const pp_scene_batch* tel, pp_traffic* traffic, int32_t consume,
+                                    const pp_follow_cfg* fcfg, const pp_follow* fstate,
+                                    const pp_lane_change_cfg* cfg, pp_lane_change* state) {
+    if (!M || !follow_ok(fcfg, fstate) || !lane_change_ok(cfg, state) || !follow_frame_ok(tel, traffic, consume))
+        return PP_ERR_ARG;
+    if (traffic->n_cars == 0) return PP_OK;
+    const ppsynth::LaneTables T = lane_tables(M->lanetab.data(), M->n);
+    const ppfollow::ArcTables AT = ppfollow::arc_tables(M->arctab.data(), M->n);
+    const int64_t S = tel->n_scenes;
+    const ppsynth::TrafficV tv = traffic_view(traffic, S);
+    for (int64_t s = 0; s < S; s++)
+        pplanechange::lane_change_scene(T, AT, S, s, tel->ego_x[s], tel->ego_y[s], tel->ego_speed_mph[s], tv, consume,
+                                        *fcfg, *fstate, *cfg, *state);
+    return PP_OK;
+}
+
+int32_t pp_rollout_lane_changing(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
+                                 const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
+                                 void* hip_stream, const pp_judge_cfg* jcfg, pp_judge* jstate,
+                                 const pp_follow_cfg* fcfg, pp_follow* fstate, const pp_lane_change_cfg* lcfg,
+                                 pp_lane_change* lstate) {
+    if (!follow_ok(fcfg, fstate) || !cfg || !follow_frame_ok(tel, traffic, cfg->consume)) return PP_ERR_ARG;
+    if (jstate && (!judge_ok(jcfg, jstate) || !judge_frame_ok(tel, traffic, res, cfg->consume))) return PP_ERR_ARG;
+    if ((lcfg || lstate) && !lane_change_ok(lcfg, lstate)) return PP_ERR_ARG;
+    return rollout_loop(M, tel, traffic, prm, cfg, res, log, device, hip_stream, jstate ? jcfg : nullptr, jstate,
+                        fcfg, fstate, lstate ? lcfg : nullptr, lstate);
 }
 
 void pp_episode_cfg_default(pp_episode_cfg* c) {

@@ -48,6 +48,7 @@
 #include "pp_synth.h"
 #include "pp_judge.h"
 #include "pp_follow.h"
+#include "pp_lanechange.h"
 #include "pp_episode.h"
 
 using namespace ppd;
@@ -58,7 +59,7 @@ using namespace ppd;
 #include "pp_k_cand.h"       // K2: run_candidate, cand_group, k_cand
 #include "pp_k_out.h"        // K3/K4: k_winner, k_winner_st, k_emit
 #include "pp_k_step.h"       // k_cand_small, k_step_small(512), k_plan_frame
-#include "pp_k_world.h"      // k_sim, k_judge, k_follow, k_synth*, map kernels, k_libm
+#include "pp_k_world.h"      // k_sim, k_judge, k_follow, k_lane_change, k_synth*, map kernels, k_libm
 #include "pp_k_math.h"       // k_math: the loop's FP64 primitives over arrays (pp_math_eval)
 
 // ================================================================================================
@@ -67,5 +68,5 @@ using namespace ppd;
 #include "pp_host_map.h"     // pp_map, DevState, StreamWS, build_map, dev_init
 #include "pp_launch.h"       // workspace, launch-shape choices, eval_impl and its launch sequences
 #include "pp_api.h"          // C ABI: params, maps, reserve, pp_eval, debug, timing, synthesis, diagnostics
-#include "pp_api_rollout.h"  // C ABI: rollouts, judge, follow
+#include "pp_api_rollout.h"  // C ABI: rollouts, judge, follow, lane change
 #include "pp_api_frame.h"    // C ABI: pp_plan_batch_host, pp_plan_reset, pp_plan_frame

@@ -458,6 +458,11 @@ bool follow_frame_ok(const pp_scene_batch* tel, const pp_traffic* traffic, int32
            traffic_ok(traffic, tel) && consume >= 1;
 }
 
+bool lane_change_ok(const pp_lane_change_cfg* c, const pp_lane_change* l) {
+    return c && l && pplanechange::cfg_ok(*c) && l->started && l->n_changes && l->last_car && l->last_dir &&
+           l->home && l->wait && l->changes && l->arc && l->gain && l->dir;
+}
+
 ppsynth::TrafficV traffic_view(const pp_traffic* t, int64_t S) {
     ppsynth::TrafficV v;
     v.S = S; v.n = t->n_cars; v.lane = t->lane; v.seg = t->seg; v.t = t->t; v.off = t->offset; v.v = t->speed;

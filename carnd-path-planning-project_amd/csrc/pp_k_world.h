@@ -1,5 +1,5 @@
 // pp_k_world.h — device: what surrounds the evaluator. The closed-loop rollout's simulator shim, judge
-// and car-following traffic (k_sim, k_judge, k_follow), scene synthesis (k_synth*), the map tables'
+// and car-following, lane-changing traffic (k_sim, k_judge, k_follow, k_lane_change), scene synthesis (k_synth*), the map tables'
 // kernels (Map::Init, src/main.cpp:89-131) and k_libm. Part of pp_eval.hip's translation unit.
 #pragma once
 
@@ -111,6 +111,21 @@ __global__ __launch_bounds__(256) void k_follow(ppsynth::LaneTables LT, ppfollow
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S) return;
     ppfollow::follow_scene(LT, AT, S, s, ego_x[s], ego_y[s], ego_speed_mph[s], tr, consume, cfg, st);
+}
+
+// Lane-changing traffic (include/pp.h pp_traffic_lane_change; csrc/pp_lanechange.h): one lane per scene,
+// every array [k * S + s]; no LDS, no scratch. Reads the pre-frame ego, the traffic with the speeds
+// k_follow has just written and k_follow's records, so it runs after k_follow and before k_judge and
+// k_sim; writes the traffic's lane, seg, t and offset and the lane-change state.
+__global__ __launch_bounds__(256) void k_lane_change(ppsynth::LaneTables LT, ppfollow::ArcTables AT, int64_t S,
+                                                     const double* ego_x, const double* ego_y,
+                                                     const double* ego_speed_mph, ppsynth::TrafficV tr, int consume,
+                                                     pp_follow_cfg fcfg, pp_follow fst, pp_lane_change_cfg cfg,
+                                                     pp_lane_change st) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    pplanechange::lane_change_scene(LT, AT, S, s, ego_x[s], ego_y[s], ego_speed_mph[s], tr, consume, fcfg, fst, cfg,
+                                    st);
 }
 
 __global__ __launch_bounds__(256) void k_synth_traffic(ppsynth::LaneTables T, uint64_t seed, int64_t first,

@@ -142,6 +142,22 @@ class Follow(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in FOLLOW_FIELDS]
 
 
+class LaneChangeCfg(C.Structure):
+    _fields_ = [("politeness", C.c_double), ("threshold", C.c_double), ("right_bias", C.c_double),
+                ("safe_brake", C.c_double), ("lateral_speed", C.c_double), ("ego_desired_speed", C.c_double),
+                ("min_interval_steps", C.c_int32), ("_pad", C.c_int32)]
+
+
+# lane-changing traffic's state (include/pp.h pp_lane_change): name, dtype, per car ([n, S]) or per scene ([S])
+LANE_CHANGE_FIELDS = [("started", "i4", False), ("n_changes", "i4", False), ("last_car", "i4", False),
+                      ("last_dir", "i4", False), ("home", "f8", True), ("wait", "i4", True), ("changes", "i4", True),
+                      ("arc", "f8", True), ("gain", "f8", True), ("dir", "i4", True)]
+
+
+class LaneChange(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _, _ in LANE_CHANGE_FIELDS]
+
+
 class EpisodeCfg(C.Structure):
     _fields_ = [("n_cars", C.c_int32), ("_pad", C.c_int32), ("ego_speed_min", C.c_double),
                 ("ego_speed_max", C.c_double), ("car_speed_min", C.c_double), ("car_speed_max", C.c_double),
@@ -194,7 +210,9 @@ EXPORTS = ["pp_params_default", "pp_num_candidates", "pp_version", "pp_map_creat
            "pp_num_lanes", "pp_max_cars", "pp_libm_eval", "pp_debug_set", "pp_debug_get",
            "pp_judge_cfg_default", "pp_judge_frame", "pp_judge_frame_host", "pp_rollout_judged",
            "pp_follow_cfg_default", "pp_traffic_follow", "pp_traffic_follow_host", "pp_rollout_reactive",
-           "pp_episode_cfg_default", "pp_synth_episode", "pp_synth_episode_host", "pp_math_eval"]
+           "pp_episode_cfg_default", "pp_synth_episode", "pp_synth_episode_host", "pp_math_eval",
+           "pp_lane_change_cfg_default", "pp_traffic_lane_change", "pp_traffic_lane_change_host",
+           "pp_rollout_lane_changing"]
 
 
 def _load():
@@ -266,6 +284,22 @@ def _load():
                                         C.c_void_p, C.POINTER(JudgeCfg), C.POINTER(Judge), C.POINTER(FollowCfg),
                                         C.POINTER(Follow)]
     lib.pp_rollout_reactive.restype = C.c_int32
+    lib.pp_lane_change_cfg_default.argtypes = [C.POINTER(LaneChangeCfg)]
+    lib.pp_lane_change_cfg_default.restype = None
+    lib.pp_traffic_lane_change.argtypes = [C.c_void_p, C.POINTER(SceneBatch), C.POINTER(Traffic), C.c_int32,
+                                           C.POINTER(FollowCfg), C.POINTER(Follow), C.POINTER(LaneChangeCfg),
+                                           C.POINTER(LaneChange), C.c_int32, C.c_void_p]
+    lib.pp_traffic_lane_change.restype = C.c_int32
+    lib.pp_traffic_lane_change_host.argtypes = [C.c_void_p, C.POINTER(SceneBatch), C.POINTER(Traffic), C.c_int32,
+                                                C.POINTER(FollowCfg), C.POINTER(Follow), C.POINTER(LaneChangeCfg),
+                                                C.POINTER(LaneChange)]
+    lib.pp_traffic_lane_change_host.restype = C.c_int32
+    lib.pp_rollout_lane_changing.argtypes = [C.c_void_p, C.POINTER(SceneBatch), C.POINTER(Traffic),
+                                             C.POINTER(Params), C.POINTER(RolloutCfg), C.POINTER(Result),
+                                             C.POINTER(RolloutLog), C.c_int32, C.c_void_p, C.POINTER(JudgeCfg),
+                                             C.POINTER(Judge), C.POINTER(FollowCfg), C.POINTER(Follow),
+                                             C.POINTER(LaneChangeCfg), C.POINTER(LaneChange)]
+    lib.pp_rollout_lane_changing.restype = C.c_int32
     lib.pp_synth_traffic.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.POINTER(SceneBatch),
                                      C.POINTER(Traffic), C.c_int32, C.c_void_p]
     lib.pp_synth_traffic.restype = C.c_int32
@@ -713,6 +747,87 @@ def rollout_reactive(m, scenes, traffic, prm, result, follow, n_frames, consume=
                                    C.byref(jcfg) if jcfg is not None else None,
                                    C.byref(J) if J is not None else None, C.byref(fcfg), C.byref(F)),
            "pp_rollout_reactive")
+
+
+def default_lane_change_cfg(**over) -> LaneChangeCfg:
+    """pp_lane_change_cfg_default, with fields overridden by keyword."""
+    c = LaneChangeCfg()
+    lib.pp_lane_change_cfg_default(C.byref(c))
+    for k, v in over.items():
+        if k not in dict(LaneChangeCfg._fields_):
+            raise KeyError(k)
+        setattr(c, k, v)
+    return c
+
+
+def alloc_lane_change(S, n=12, xp="numpy", device=None):
+    """Zero-filled lane-change state of S scenes x n cars (every scene a fresh episode)."""
+    if xp == "numpy":
+        mk = lambda sh, dt: np.zeros(sh, dt)
+    else:
+        import torch
+        tdt = {"f8": torch.float64, "i4": torch.int32}
+        mk = lambda sh, dt: torch.zeros(sh, dtype=tdt[dt], device=device)
+    return {k: mk((n, S) if per_car else (S,), dt) for k, dt, per_car in LANE_CHANGE_FIELDS}
+
+
+def lane_change_struct(l) -> LaneChange:
+    L = LaneChange()
+    for k, _, _ in LANE_CHANGE_FIELDS:
+        setattr(L, k, _ptr(l[k]))
+    return L
+
+
+def lane_change_to_numpy(l):
+    return {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in l.items()}
+
+
+def traffic_lane_change(m, scenes, traffic, follow, lane_change, consume=3, fcfg=None, cfg=None, host=None,
+                        device=0, stream=None):
+    """pp_traffic_lane_change / pp_traffic_lane_change_host: the lane changes of one frame, after
+    traffic_follow of the same frame; traffic's lane, seg, t and offset and `lane_change` are updated in
+    place. host=None picks the host twin when the arrays are numpy."""
+    if host is None:
+        host = isinstance(scenes["ego_x"], np.ndarray)
+    fcfg = fcfg if fcfg is not None else default_follow_cfg()
+    cfg = cfg if cfg is not None else default_lane_change_cfg()
+    n = int(traffic["n_cars"])
+    assert follow["desired"].shape[0] >= n, "follow state holds fewer cars than the traffic"
+    assert lane_change["home"].shape[0] >= n, "lane-change state holds fewer cars than the traffic"
+    b, T, F, L = scene_struct(scenes), traffic_struct(traffic), follow_struct(follow), lane_change_struct(lane_change)
+    if host:
+        _check(lib.pp_traffic_lane_change_host(m.handle, C.byref(b), C.byref(T), consume, C.byref(fcfg), C.byref(F),
+                                               C.byref(cfg), C.byref(L)), "pp_traffic_lane_change_host")
+    else:
+        _check(lib.pp_traffic_lane_change(m.handle, C.byref(b), C.byref(T), consume, C.byref(fcfg), C.byref(F),
+                                          C.byref(cfg), C.byref(L), device, stream), "pp_traffic_lane_change")
+
+
+def rollout_lane_changing(m, scenes, traffic, prm, result, follow, lane_change, n_frames, consume=3,
+                          sensor_range=300.0, log=None, judge=None, jcfg=None, fcfg=None, lcfg=None, device=0,
+                          stream=None):
+    """pp_rollout_lane_changing: rollout_reactive() whose traffic also changes lanes (lane-change state
+    updated in place); lane_change=None: exactly rollout_reactive()."""
+    n = int(traffic["n_cars"])
+    assert follow["desired"].shape[0] >= n, "follow state holds fewer cars than the traffic"
+    b, T, R, F = scene_struct(scenes), traffic_struct(traffic), result_struct(result), follow_struct(follow)
+    rc = RolloutCfg(n_frames, consume, float(sensor_range))
+    fcfg = fcfg if fcfg is not None else default_follow_cfg()
+    J = judge_struct(judge) if judge is not None else None
+    if judge is not None and jcfg is None:
+        jcfg = default_judge_cfg()
+    LS = None
+    if lane_change is not None:
+        assert lane_change["home"].shape[0] >= n, "lane-change state holds fewer cars than the traffic"
+        LS = lane_change_struct(lane_change)
+        lcfg = lcfg if lcfg is not None else default_lane_change_cfg()
+    L = log_struct(log) if log is not None else None
+    _check(lib.pp_rollout_lane_changing(m.handle, C.byref(b), C.byref(T), C.byref(prm), C.byref(rc), C.byref(R),
+                                        C.byref(L) if L is not None else None, device, stream,
+                                        C.byref(jcfg) if jcfg is not None else None,
+                                        C.byref(J) if J is not None else None, C.byref(fcfg), C.byref(F),
+                                        C.byref(lcfg) if LS is not None else None,
+                                        C.byref(LS) if LS is not None else None), "pp_rollout_lane_changing")
 
 
 def plan_reset(m, device=0):

@@ -438,6 +438,81 @@ int32_t pp_rollout_reactive(pp_map* m, pp_scene_batch* telemetry, pp_traffic* tr
                             const pp_judge_cfg* jcfg, pp_judge* jstate,
                             const pp_follow_cfg* fcfg, pp_follow* fstate);
 
+/* ---- lane-changing traffic: a car moves to a neighbour lane when MOBIL says so ----------------- */
+/* Reactive traffic never leaves its lane: a faster car queues behind a slower one for ever and no car
+ * ever moves into the ego's lane. Here the cars change lanes by MOBIL ("minimising overall braking
+ * induced by lane changes") on the accelerations of the model above. One call runs AFTER
+ * pp_traffic_follow of the same frame and reads that call's records (desired, leader, gap, ego_seg)
+ * and the speeds it wrote. THIS LIBRARY'S OWN definitions (DESIGN.md "Lane-changing traffic" states
+ * them in full). In short, per call and scene: every car's offset returns to its home value at
+ * lateral_speed and its wait runs down; a car that is not parked, not waiting and not in transit
+ * (offset == home) is a candidate for lane - 1 and lane + 1; on the target lane it would get the new
+ * leader n and the new follower f (other cars of that lane, and the ego where it occupies it), and
+ * leave its old follower o behind. With a the IDM acceleration before and a' after the change:
+ *   safe    = net gaps to n and f >= min_gap, a_f' >= -safe_brake, a_j' >= -safe_brake
+ *   gain    = (a_j' - a_j) + politeness ((a_f' - a_f) + (a_o' - a_o))     (the ego never gains)
+ *   surplus = gain - threshold -/+ right_bias
+ * and the ONE candidate of the scene with the largest surplus > 0 is placed on its new lane at the
+ * nearest point of that lane's centre, with the offset that keeps it where it is; it then waits
+ * min_interval_steps. A car in transit counts only in its new lane. */
+typedef struct pp_lane_change_cfg {
+    double  politeness;            /* 0.3: weight of the other drivers' gain                       */
+    double  threshold;             /* 0.2 m/s^2: the gain a change must exceed (+inf: never change) */
+    double  right_bias;            /* 0.0 m/s^2: added to the threshold of a change to lane - 1,
+                                      subtracted from that of a change to lane + 1                 */
+    double  safe_brake;            /* 3.0 m/s^2: no change makes anyone brake harder than this     */
+    double  lateral_speed;         /* 1.5 m/s: how fast the offset returns to its home value       */
+    double  ego_desired_speed;     /* 22.2 m/s: v0 of the ego where it would become the new follower */
+    int32_t min_interval_steps;    /* 250: driven steps a car waits after beginning a change       */
+    int32_t _pad;
+} pp_lane_change_cfg;              /* politeness >= 0; safe_brake, lateral_speed, ego_desired_speed
+                                      > 0; min_interval_steps >= 0; no NaN                         */
+
+/* Lane-change state of a batch (SoA, caller owned; device resident for pp_traffic_lane_change and
+ * pp_rollout_lane_changing, host memory for pp_traffic_lane_change_host), S = the telemetry's
+ * n_scenes, per-car arrays [j * S + s] for j < traffic.n_cars. A scene whose started[s] is 0 on
+ * entry starts a fresh episode: its cars' home offsets are captured from traffic.offset and every
+ * other field of it is written by the call, so a zero-filled state is a valid start and a state is
+ * reused by zeroing `started` alone. */
+typedef struct pp_lane_change {
+    int32_t* started;              /* 0 = fresh episode; set to 1 by the call                      */
+    int32_t* n_changes;            /* changes begun in this scene so far                           */
+    int32_t* last_car;             /* car + 1 that began a change in the LAST call, 0: none        */
+    int32_t* last_dir;             /* -1 / +1 of that change, 0: none                              */
+    double*  home;                 /* [j * S + s] the offset the car returns to (captured fresh)   */
+    int32_t* wait;                 /* [j * S + s] driven steps until the car may change again      */
+    int32_t* changes;              /* [j * S + s] changes this car has begun                       */
+    double*  arc;                  /* [j * S + s] staging: the car's arc on its own lane           */
+    double*  gain;                 /* [j * S + s] record: best surplus of this call, -inf: not eligible */
+    int32_t* dir;                  /* [j * S + s] record: direction of that surplus, 0: none       */
+} pp_lane_change;
+
+void    pp_lane_change_cfg_default(pp_lane_change_cfg* c);
+/* Lets the traffic change lanes for ONE frame. Call it after pp_traffic_follow of the same frame
+ * (same telemetry, traffic, consume, fcfg and fstate) and before pp_judge_frame and before moving
+ * the traffic. Writes traffic->lane, seg, t, offset and `state`; never traffic->speed or `fstate`. A
+ * scene whose fstate->started is 0 is left alone; with no cars nothing is touched. PP_ERR_ARG (before
+ * any HIP call) for a NULL argument or state array, a follow cfg or state pp_traffic_follow would
+ * refuse, a cfg outside the ranges above, or consume < 1. Device pointers; asynchronous on
+ * hip_stream. */
+int32_t pp_traffic_lane_change(pp_map* m, const pp_scene_batch* telemetry, pp_traffic* traffic, int32_t consume,
+                               const pp_follow_cfg* fcfg, const pp_follow* fstate,
+                               const pp_lane_change_cfg* cfg, pp_lane_change* state,
+                               int32_t device, void* hip_stream);
+/* The same on the host (host pointers; the same arithmetic, bit for bit). */
+int32_t pp_traffic_lane_change_host(const pp_map* m, const pp_scene_batch* telemetry, pp_traffic* traffic,
+                                    int32_t consume, const pp_follow_cfg* fcfg, const pp_follow* fstate,
+                                    const pp_lane_change_cfg* cfg, pp_lane_change* state);
+/* pp_rollout_reactive with lane changes: per frame pp_eval, the follow update, the lane changes, the
+ * judge (only when jstate is not NULL), then the simulator, on the one stream. lcfg and lstate both
+ * NULL: exactly pp_rollout_reactive. */
+int32_t pp_rollout_lane_changing(pp_map* m, pp_scene_batch* telemetry, pp_traffic* traffic,
+                                 const pp_params* prm, const pp_rollout_cfg* cfg, pp_result* result,
+                                 pp_rollout_log* log, int32_t device, void* hip_stream,
+                                 const pp_judge_cfg* jcfg, pp_judge* jstate,
+                                 const pp_follow_cfg* fcfg, pp_follow* fstate,
+                                 const pp_lane_change_cfg* lcfg, pp_lane_change* lstate);
+
 /* Rollout start state: writes the synthetic scenes of pp_synth_scenes (same seed and indices)
  * into `telemetry` and their traffic into `out` (n_cars = 12): car j starts exactly where the
  * scene reports it, on its lane with its lateral offset and speed. Empties the car table of
