@@ -305,25 +305,15 @@ int32_t pp_synth_scenes(pp_map* M, uint64_t seed, int64_t first_scene, pp_scene_
     if (!M || !out || device < 0 || device >= kMaxDev || out->n_scenes < 0 || first_scene < 0) return PP_ERR_ARG;
     if (out->car_stride < ppsynth::kSynthCars) return PP_ERR_ARG;
     if (out->n_scenes == 0) return PP_OK;
-    DeviceGuard g(device);
-    ppsynth::LaneTables T;
-    {
-        std::lock_guard<std::mutex> lk(M->mu);
-        const int rc = dev_init(M, device);
-        if (rc) return rc;
-        T = lane_tables(M->dev[device].tab.lanetab.get(), M->n);
-    }
+    const WorldDev W(M, device, false);
+    if (W.rc) return W.rc;
     const ppsynth::OutBatch o = out_batch(out);
-    const int threads = 256;
-    const int64_t blocks = (o.S + threads - 1) / threads;
-    hipLaunchKernelGGL(k_synth, dim3((unsigned)blocks), dim3(threads), 0, (hipStream_t)hip_stream, T, seed, first_scene, o);
-    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-    return PP_OK;
+    return launch_scenes(k_synth, o.S, hip_stream, W.T, seed, first_scene, o);
 }
 
 int32_t pp_synth_scenes_host(const pp_map* M, uint64_t seed, int64_t first_scene, pp_scene_batch* out) {
     if (!M || !out || out->n_scenes < 0 || first_scene < 0 || out->car_stride < ppsynth::kSynthCars) return PP_ERR_ARG;
-    const ppsynth::LaneTables T = lane_tables(M->lanetab.data(), M->n);
+    const ppsynth::LaneTables T = host_tables(M).T;
     const ppsynth::OutBatch o = out_batch(out);
     for (int64_t s = 0; s < o.S; s++) ppsynth::synth_scene(T, seed, first_scene + s, s, o);
     return PP_OK;
@@ -336,21 +326,11 @@ int32_t pp_synth_traffic(pp_map* M, uint64_t seed, int64_t first_scene, pp_scene
         (tel->tab_valid && (tel->tab_slots < ppsynth::kSynthCars || tel->tab_slots > PP_MAX_CARS)))
         return PP_ERR_ARG;
     if (tel->n_scenes == 0) return PP_OK;
-    DeviceGuard g(device);
-    ppsynth::LaneTables T;
-    {
-        std::lock_guard<std::mutex> lk(M->mu);
-        const int rc = dev_init(M, device);
-        if (rc) return rc;
-        T = lane_tables(M->dev[device].tab.lanetab.get(), M->n);
-    }
+    const WorldDev W(M, device, false);
+    if (W.rc) return W.rc;
     out->n_cars = ppsynth::kSynthCars;
     const ppsynth::OutBatch o = out_batch(tel);
-    const int64_t blocks = (o.S + 255) / 256;
-    hipLaunchKernelGGL(k_synth_traffic, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, T,
-                       seed, first_scene, o, traffic_view(out, o.S), *tel);
-    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-    return PP_OK;
+    return launch_scenes(k_synth_traffic, o.S, hip_stream, W.T, seed, first_scene, o, traffic_view(out, o.S), *tel);
 }
 
 int32_t pp_synth_traffic_host(const pp_map* M, uint64_t seed, int64_t first_scene, pp_scene_batch* tel,
@@ -359,7 +339,7 @@ int32_t pp_synth_traffic_host(const pp_map* M, uint64_t seed, int64_t first_scen
         !traffic_ok(out, tel) ||
         (tel->tab_valid && (tel->tab_slots < ppsynth::kSynthCars || tel->tab_slots > PP_MAX_CARS)))
         return PP_ERR_ARG;
-    const ppsynth::LaneTables T = lane_tables(M->lanetab.data(), M->n);
+    const ppsynth::LaneTables T = host_tables(M).T;
     out->n_cars = ppsynth::kSynthCars;
     const ppsynth::OutBatch o = out_batch(tel);
     const ppsynth::TrafficV tv = traffic_view(out, o.S);

@@ -19,6 +19,7 @@
 #pragma once
 #include <stdint.h>
 #include <math.h>
+#include <string.h>
 
 #include "../../include/pp.h"
 #include "pp_synth.h"
@@ -27,6 +28,20 @@
 namespace ppepisode {
 
 constexpr uint32_t kTag = 0xE9150DE1u;     // the stream's fourth counter word
+
+// pp_episode_cfg_default's values (host only)
+inline void cfg_default(pp_episode_cfg* c) {
+    memset(c, 0, sizeof(*c));
+    c->n_cars = 12;
+    c->ego_speed_min = 0;
+    c->ego_speed_max = 20;
+    c->car_speed_min = 5;
+    c->car_speed_max = 25;
+    c->ahead_share = 0.75;
+    c->extra_gap = 40;
+    c->offset_jitter = 0.3;
+    c->gap_slack = 1e-6;
+}
 
 // true also rejects NaN: every comparison is written so that a NaN fails it
 PP_HD inline bool cfg_ok(const pp_episode_cfg& c) {

@@ -19,8 +19,10 @@
 // output frame, winner record and map staging (pp_k_frame.h); K0/K1 scene preparation
 // (pp_k_prep.h); phase A's spline slots (pp_k_spline.h); K2 candidates (pp_k_cand.h); K3/K4 output
 // (pp_k_out.h); the fused small-batch and frame kernels (pp_k_step.h); rollout, synthesis, map and
-// libm kernels (pp_k_world.h); the primitives' test kernel (pp_k_math.h). Then the host side (pp_host_map.h, pp_launch.h, pp_api.h,
-// pp_api_rollout.h, pp_api_frame.h).
+// libm kernels (pp_k_world.h); the primitives' test kernel (pp_k_math.h). Then the host side: maps,
+// device resources and the world stages' tables and per-scene launch (pp_host_map.h), pp_eval's
+// launches (pp_launch.h), the C ABI (pp_api.h, pp_api_rollout.h, pp_api_frame.h). The world stages'
+// shared arithmetic and default configurations are pp_judge.h, pp_follow.h, pp_lanechange.h, pp_episode.h.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -65,7 +67,7 @@ using namespace ppd;
 // ================================================================================================
 // host side (one translation unit with the kernels above, so the launches see them)
 // ================================================================================================
-#include "pp_host_map.h"     // pp_map, DevState, StreamWS, build_map, dev_init
+#include "pp_host_map.h"     // pp_map, DevState, StreamWS, build_map, dev_init, WorldDev, launch_scenes
 #include "pp_launch.h"       // workspace, launch-shape choices, eval_impl and its launch sequences
 #include "pp_api.h"          // C ABI: params, maps, reserve, pp_eval, debug, timing, synthesis, diagnostics
 #include "pp_api_rollout.h"  // C ABI: rollouts, judge, follow, lane change

@@ -10,6 +10,7 @@
 #pragma once
 #include <stdint.h>
 #include <math.h>
+#include <string.h>
 
 #include "../../include/pp.h"
 #include "pp_synth.h"
@@ -34,6 +35,21 @@ inline ArcTables arc_tables(const double* t, int n) {
     ArcTables A;
     A.cum = t; A.loop = t + PP_NUM_LANES * n;
     return A;
+}
+
+// pp_follow_cfg_default's values (host only)
+inline void cfg_default(pp_follow_cfg* c) {
+    memset(c, 0, sizeof(*c));
+    c->max_acc = 2.0;
+    c->comfort_brake = 3.0;
+    c->max_brake = 8.0;
+    c->time_headway = 1.2;
+    c->min_gap = 2.0;
+    c->gap_floor = 0.5;
+    c->horizon = 150;
+    c->car_length = c->ego_length = 4.5;
+    c->lateral_reach = 2.0;
+    c->react_to_ego = 1;
 }
 
 PP_HD inline bool cfg_ok(const pp_follow_cfg& c) {

@@ -435,11 +435,13 @@ bool traffic_ok(const pp_traffic* t, const pp_scene_batch* b) {
            t->offset && t->speed;
 }
 
-bool judge_ok(const pp_judge_cfg* c, const pp_judge* j) {
-    return c && j && ppjudge::cfg_ok(*c) && j->steps && j->flags && j->count && j->first_step &&
-           j->first_car && j->seg_hint && j->off_run && j->head_x && j->head_y && j->ring_vx && j->ring_vy &&
-           j->dist && j->clean_dist && j->min_sep && j->max_speed_mph && j->max_acc && j->max_jerk;
+// a stage's state has every array (the pointers only); *_ok: that and a configuration in range
+bool judge_state_ok(const pp_judge* j) {
+    return j && j->steps && j->flags && j->count && j->first_step && j->first_car && j->seg_hint && j->off_run &&
+           j->head_x && j->head_y && j->ring_vx && j->ring_vy && j->dist && j->clean_dist && j->min_sep &&
+           j->max_speed_mph && j->max_acc && j->max_jerk;
 }
+bool judge_ok(const pp_judge_cfg* c, const pp_judge* j) { return c && ppjudge::cfg_ok(*c) && judge_state_ok(j); }
 
 // what the judge reads of a frame: the ego pose, the traffic, the plan
 bool judge_frame_ok(const pp_scene_batch* tel, const pp_traffic* traffic, const pp_result* plan, int32_t consume) {
@@ -447,10 +449,10 @@ bool judge_frame_ok(const pp_scene_batch* tel, const pp_traffic* traffic, const 
            traffic_ok(traffic, tel) && plan->n_out && plan->next_x && plan->next_y && consume >= 1;
 }
 
-bool follow_ok(const pp_follow_cfg* c, const pp_follow* f) {
-    return c && f && ppfollow::cfg_ok(*c) && f->started && f->ego_seg && f->desired && f->next_speed &&
-           f->leader && f->gap;
+bool follow_state_ok(const pp_follow* f) {
+    return f && f->started && f->ego_seg && f->desired && f->next_speed && f->leader && f->gap;
 }
+bool follow_ok(const pp_follow_cfg* c, const pp_follow* f) { return c && ppfollow::cfg_ok(*c) && follow_state_ok(f); }
 
 // what the follow update reads of a frame: the ego's position and speed, the traffic
 bool follow_frame_ok(const pp_scene_batch* tel, const pp_traffic* traffic, int32_t consume) {
@@ -494,6 +496,37 @@ int dev_init(pp_map* M, int device) {
 int arc_init(pp_map* M, int device) {
     DevState& D = M->dev[device];
     return D.arctab ? PP_OK : upload(D.arctab, M->arctab);
+}
+
+// The world stages' two table views. host_tables: over the map's host arrays, for the host twins.
+struct WorldTables {
+    ppsynth::LaneTables T;
+    ppfollow::ArcTables AT;
+};
+WorldTables host_tables(const pp_map* M) {
+    return {lane_tables(M->lanetab.data(), M->n), ppfollow::arc_tables(M->arctab.data(), M->n)};
+}
+// The same over the device copies, for a world kernel's launch: makes `device` current for its own
+// lifetime and, under M->mu, uploads what is missing (the arc prefix only where want_arc; AT is null
+// without it). rc: PP_OK, or why there are no tables.
+struct WorldDev : WorldTables {
+    DeviceGuard g;
+    int rc;
+    WorldDev(pp_map* M, int device, bool want_arc) : WorldTables{{}, {nullptr, nullptr}}, g(device) {
+        std::lock_guard<std::mutex> lk(M->mu);
+        rc = dev_init(M, device);
+        if (!rc && want_arc) rc = arc_init(M, device);
+        if (rc) return;
+        T = lane_tables(M->dev[device].tab.lanetab.get(), M->n);
+        if (want_arc) AT = ppfollow::arc_tables(M->dev[device].arctab.get(), M->n);
+    }
+};
+
+// a kernel of one lane per scene in blocks of 256 on `st`; PP_ERR_HIP where the launch is refused
+template <class K, class... Args>
+int launch_scenes(K kernel, int64_t S, void* st, const Args&... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, (hipStream_t)st, args...);
+    return hipGetLastError() == hipSuccess ? PP_OK : PP_ERR_HIP;
 }
 
 }  // namespace

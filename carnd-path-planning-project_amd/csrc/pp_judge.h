@@ -10,6 +10,7 @@
 #pragma once
 #include <stdint.h>
 #include <math.h>
+#include <string.h>
 
 #include "../../include/pp.h"
 #include "pp_synth.h"
@@ -19,6 +20,20 @@ namespace ppjudge {
 constexpr double kDt = 0.02;               // one driven step (the simulator's 50 Hz)
 constexpr int kRingMask = PP_JUDGE_RING - 1;
 static_assert((PP_JUDGE_RING & kRingMask) == 0, "PP_JUDGE_RING must be a power of two");
+
+// pp_judge_cfg_default's values (host only)
+inline void cfg_default(pp_judge_cfg* c) {
+    memset(c, 0, sizeof(*c));
+    c->speed_limit_mph = 50;
+    c->max_acc = 10;
+    c->max_jerk = 10;
+    c->ego_length = c->car_length = 4.5;
+    c->ego_width = c->car_width = 2.0;
+    c->lane_tol = 1.0;
+    c->acc_window = 10;
+    c->jerk_window = 50;
+    c->off_lane_steps = 150;
+}
 
 PP_HD inline bool cfg_ok(const pp_judge_cfg& c) {
     return c.acc_window >= 1 && c.jerk_window >= 1 && c.acc_window <= kRingMask &&

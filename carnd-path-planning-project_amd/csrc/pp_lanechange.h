@@ -14,12 +14,25 @@
 #pragma once
 #include <stdint.h>
 #include <math.h>
+#include <string.h>
 
 #include "../../include/pp.h"
 #include "pp_synth.h"
 #include "pp_follow.h"
 
 namespace pplanechange {
+
+// pp_lane_change_cfg_default's values (host only)
+inline void cfg_default(pp_lane_change_cfg* c) {
+    memset(c, 0, sizeof(*c));
+    c->politeness = 0.3;
+    c->threshold = 0.2;
+    c->right_bias = 0.0;
+    c->safe_brake = 3.0;
+    c->lateral_speed = 1.5;
+    c->ego_desired_speed = 22.2;
+    c->min_interval_steps = 250;
+}
 
 PP_HD inline bool cfg_ok(const pp_lane_change_cfg& c) {
     return c.politeness >= 0 && c.threshold == c.threshold && c.right_bias == c.right_bias && c.safe_brake > 0 &&

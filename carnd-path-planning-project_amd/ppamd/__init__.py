@@ -110,7 +110,8 @@ class JudgeCfg(C.Structure):
                 ("jerk_window", C.c_int32), ("off_lane_steps", C.c_int32), ("_pad", C.c_int32)]
 
 
-# the rollout judge's state (include/pp.h pp_judge): name, dtype, leading dimension (None: [S])
+# The states' field tables: name, dtype, leading dimension (None: [S], a number k: [k, S], "n": [n, S],
+# one row per car). The rollout judge's state (include/pp.h pp_judge):
 JUDGE_RING = 64
 INC_KINDS = ["COLLISION", "SPEED", "ACC", "JERK", "OFF_LANE"]      # kind k is flag bit 1 << k
 INC_COLLISION, INC_SPEED, INC_ACC, INC_JERK, INC_OFF_LANE = (1 << k for k in range(5))
@@ -133,9 +134,9 @@ class FollowCfg(C.Structure):
                 ("lateral_reach", C.c_double), ("react_to_ego", C.c_int32), ("_pad", C.c_int32)]
 
 
-# reactive traffic's state (include/pp.h pp_follow): name, dtype, per car ([n, S]) or per scene ([S])
-FOLLOW_FIELDS = [("started", "i4", False), ("ego_seg", "i4", False), ("desired", "f8", True),
-                 ("next_speed", "f8", True), ("leader", "i4", True), ("gap", "f8", True)]
+# reactive traffic's state (include/pp.h pp_follow)
+FOLLOW_FIELDS = [("started", "i4", None), ("ego_seg", "i4", None), ("desired", "f8", "n"),
+                 ("next_speed", "f8", "n"), ("leader", "i4", "n"), ("gap", "f8", "n")]
 
 
 class Follow(C.Structure):
@@ -148,10 +149,10 @@ class LaneChangeCfg(C.Structure):
                 ("min_interval_steps", C.c_int32), ("_pad", C.c_int32)]
 
 
-# lane-changing traffic's state (include/pp.h pp_lane_change): name, dtype, per car ([n, S]) or per scene ([S])
-LANE_CHANGE_FIELDS = [("started", "i4", False), ("n_changes", "i4", False), ("last_car", "i4", False),
-                      ("last_dir", "i4", False), ("home", "f8", True), ("wait", "i4", True), ("changes", "i4", True),
-                      ("arc", "f8", True), ("gain", "f8", True), ("dir", "i4", True)]
+# lane-changing traffic's state (include/pp.h pp_lane_change)
+LANE_CHANGE_FIELDS = [("started", "i4", None), ("n_changes", "i4", None), ("last_car", "i4", None),
+                      ("last_dir", "i4", None), ("home", "f8", "n"), ("wait", "i4", "n"), ("changes", "i4", "n"),
+                      ("arc", "f8", "n"), ("gain", "f8", "n"), ("dir", "i4", "n")]
 
 
 class LaneChange(C.Structure):
@@ -386,6 +387,50 @@ def _ptr(a):
     return a.data_ptr()
 
 
+def _ref(x):
+    """byref of a ctypes structure; None (a null pointer) for None."""
+    return C.byref(x) if x is not None else None
+
+
+def _zeros(xp, device):
+    """mk(shape, dtype code): a zero array, numpy on the host or torch on `device` (torch holds the
+    u4 words as int32: it has no uint32 arithmetic; *_to_numpy view them back)."""
+    if xp == "numpy":
+        return lambda sh, dt: np.zeros(sh, dt)
+    import torch
+    tdt = {"f8": torch.float64, "i4": torch.int32, "u4": torch.int32}
+    return lambda sh, dt: torch.zeros(sh, dtype=tdt[dt], device=device)
+
+
+def _alloc_state(fields, S, n, xp, device):
+    """Zero arrays of a field table (JUDGE_FIELDS, FOLLOW_FIELDS, LANE_CHANGE_FIELDS)."""
+    mk = _zeros(xp, device)
+    return {k: mk((S,) if lead is None else (n if lead == "n" else lead, S), dt) for k, dt, lead in fields}
+
+
+def _struct(cls, names, d, optional=False):
+    """A pointer structure from the arrays of dict d; optional: a missing array is a null pointer."""
+    s = cls()
+    for k in names:
+        setattr(s, k, _ptr(d.get(k) if optional else d[k]))
+    return s
+
+
+def _to_numpy(d):
+    return {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in d.items()}
+
+
+def _default_cfg(cls, fill, over):
+    """A configuration structure filled by the library's pp_*_cfg_default, fields overridden by keyword."""
+    c = cls()
+    fill(C.byref(c))
+    for k, v in over.items():
+        if k not in dict(cls._fields_):
+            raise KeyError(k)
+        setattr(c, k, v)
+    return c
+
+
 class Map:
     """Map::Init (src/main.cpp:89-131) over waypoint x/y; lane geometry uploaded per device."""
 
@@ -449,19 +494,13 @@ CAR_FIELDS_F = ["car_x", "car_y", "car_vx", "car_vy"]
 
 def alloc_scenes(S, car_stride=12, xp="numpy", device=None):
     """SoA scene arrays (numpy on host, or torch on `device`)."""
-    if xp == "numpy":
-        zf = lambda *sh: np.zeros(sh, np.float64)
-        zi = lambda *sh: np.zeros(sh, np.int32)
-    else:
-        import torch
-        zf = lambda *sh: torch.zeros(sh, dtype=torch.float64, device=device)
-        zi = lambda *sh: torch.zeros(sh, dtype=torch.int32, device=device)
-    d = {k: zf(S) for k in SCENE_FIELDS_F}
-    d.update({k: zi(S) for k in SCENE_FIELDS_I})
-    d["prev_x"] = zf(PREV_KEEP, S)
-    d["prev_y"] = zf(PREV_KEEP, S)
-    d["car_id"] = zi(car_stride, S)
-    d.update({k: zf(car_stride, S) for k in CAR_FIELDS_F})
+    mk = _zeros(xp, device)
+    d = {k: mk((S,), "f8") for k in SCENE_FIELDS_F}
+    d.update({k: mk((S,), "i4") for k in SCENE_FIELDS_I})
+    d["prev_x"] = mk((PREV_KEEP, S), "f8")
+    d["prev_y"] = mk((PREV_KEEP, S), "f8")
+    d["car_id"] = mk((car_stride, S), "i4")
+    d.update({k: mk((car_stride, S), "f8") for k in CAR_FIELDS_F})
     return d
 
 
@@ -479,39 +518,29 @@ def scene_struct(d) -> SceneBatch:
     return b
 
 
-def _mk(xp, device):
-    if xp == "numpy":
-        return (lambda sh: np.zeros(sh, np.float64)), (lambda sh: np.zeros(sh, np.int32))
-    import torch
-    return (lambda sh: torch.zeros(sh, dtype=torch.float64, device=device),
-            lambda sh: torch.zeros(sh, dtype=torch.int32, device=device))
-
-
 def add_car_table(d, slots=12, xp="numpy", device=None):
     """Adds the persistent car table (include/pp.h tab_*: `slots` slots per scene, slot j = id j,
     empty) to a scene dict."""
     S = int(d["ego_x"].shape[0])
-    zf, zi = _mk(xp, device)
+    mk = _zeros(xp, device)
     for k in TABLE_FIELDS_I:
-        d[k] = zi((slots, S))
+        d[k] = mk((slots, S), "i4")
     for k in TABLE_FIELDS_F:
-        d[k] = zf((slots, S))
+        d[k] = mk((slots, S), "f8")
     for j in range(slots):
         d["tab_id"][j] = j
     return d
 
 
 def alloc_traffic(S, n=12, xp="numpy", device=None):
-    zf, zi = _mk(xp, device)
-    return {"n_cars": 0, "lane": zi((n, S)), "seg": zi((n, S)), "t": zf((n, S)),
-            "offset": zf((n, S)), "speed": zf((n, S))}
+    mk = _zeros(xp, device)
+    return {"n_cars": 0, "lane": mk((n, S), "i4"), "seg": mk((n, S), "i4"), "t": mk((n, S), "f8"),
+            "offset": mk((n, S), "f8"), "speed": mk((n, S), "f8")}
 
 
 def traffic_struct(t) -> Traffic:
-    T = Traffic()
+    T = _struct(Traffic, ["lane", "seg", "t", "offset", "speed"], t)
     T.n_cars = int(t["n_cars"])
-    for k in ["lane", "seg", "t", "offset", "speed"]:
-        setattr(T, k, _ptr(t[k]))
     return T
 
 
@@ -538,13 +567,7 @@ def synth_traffic_host(m, S, seed=0x5EED0001, first=0, car_stride=12, slots=12):
 
 def default_episode_cfg(**over) -> EpisodeCfg:
     """pp_episode_cfg_default, with fields overridden by keyword."""
-    c = EpisodeCfg()
-    lib.pp_episode_cfg_default(C.byref(c))
-    for k, v in over.items():
-        if k not in dict(EpisodeCfg._fields_):
-            raise KeyError(k)
-        setattr(c, k, v)
-    return c
+    return _default_cfg(EpisodeCfg, lib.pp_episode_cfg_default, over)
 
 
 def _episode_args(S, cfg, xp, device, judge, follow):
@@ -567,9 +590,8 @@ def synth_episode(m, S, seed=0x5EED0001, first=0, cfg=None, fcfg=None, device=0,
     import torch
     cfg, d, t, J, F = _episode_args(S, cfg, "torch", torch.device("cuda", device), judge, follow)
     b, T = scene_struct(d), traffic_struct(t)
-    _check(lib.pp_synth_episode(m.handle, seed, first, C.byref(cfg), C.byref(fcfg) if fcfg is not None else None,
-                                C.byref(b), C.byref(T), C.byref(J) if J is not None else None,
-                                C.byref(F) if F is not None else None, device, stream), "pp_synth_episode")
+    _check(lib.pp_synth_episode(m.handle, seed, first, _ref(cfg), _ref(fcfg), _ref(b), _ref(T), _ref(J), _ref(F),
+                                device, stream), "pp_synth_episode")
     t["n_cars"] = T.n_cars
     return d, t
 
@@ -578,20 +600,14 @@ def synth_episode_host(m, S, seed=0x5EED0001, first=0, cfg=None, fcfg=None, judg
     """pp_synth_episode_host: synth_episode on the host (numpy arrays, the same bits)."""
     cfg, d, t, J, F = _episode_args(S, cfg, "numpy", None, judge, follow)
     b, T = scene_struct(d), traffic_struct(t)
-    _check(lib.pp_synth_episode_host(m.handle, seed, first, C.byref(cfg), C.byref(fcfg) if fcfg is not None else None,
-                                     C.byref(b), C.byref(T), C.byref(J) if J is not None else None,
-                                     C.byref(F) if F is not None else None), "pp_synth_episode_host")
+    _check(lib.pp_synth_episode_host(m.handle, seed, first, _ref(cfg), _ref(fcfg), _ref(b), _ref(T), _ref(J),
+                                     _ref(F)), "pp_synth_episode_host")
     t["n_cars"] = T.n_cars
     return d, t
 
 
 def alloc_log(F, S, N=50, xp="numpy", device=None, plans=True):
-    if xp == "numpy":
-        mk = lambda sh, dt: np.zeros(sh, dt)
-    else:
-        import torch
-        tdt = {"f8": torch.float64, "i4": torch.int32, "u4": torch.int32}
-        mk = lambda sh, dt: torch.zeros(sh, dtype=tdt[dt], device=device)
+    mk = _zeros(xp, device)
     lg = {k: mk((F, S), dt) for k, dt in LOG_FIELDS}
     if plans:
         lg["plan_x"] = mk((F, N, S), "f8")
@@ -600,54 +616,51 @@ def alloc_log(F, S, N=50, xp="numpy", device=None, plans=True):
 
 
 def log_struct(lg) -> RolloutLog:
-    L = RolloutLog()
-    for k, _ in LOG_FIELDS:
-        setattr(L, k, _ptr(lg.get(k)))
-    L.plan_x, L.plan_y = _ptr(lg.get("plan_x")), _ptr(lg.get("plan_y"))
-    return L
+    return _struct(RolloutLog, [k for k, _ in LOG_FIELDS] + ["plan_x", "plan_y"], lg, optional=True)
 
 
 def rollout(m, scenes, traffic, prm, result, n_frames, consume=3, sensor_range=300.0, log=None,
             device=0, stream=None):
     """pp_rollout: n_frames closed-loop frames on the GPU; scenes/traffic/result updated in place."""
+    _rollout(lib.pp_rollout, "pp_rollout", m, scenes, traffic, prm, result, n_frames, consume, sensor_range, log,
+             device, stream)
+
+
+def _rollout(entry, what, m, scenes, traffic, prm, result, n_frames, consume, sensor_range, log, device, stream,
+             *stages):
+    """The four rollouts' call: their common arguments, then the entry point's own tail `stages`
+    (configuration and state structures in its order; None: a null pointer)."""
     b, T, R = scene_struct(scenes), traffic_struct(traffic), result_struct(result)
     cfg = RolloutCfg(n_frames, consume, float(sensor_range))
     L = log_struct(log) if log is not None else None
-    _check(lib.pp_rollout(m.handle, C.byref(b), C.byref(T), C.byref(prm), C.byref(cfg), C.byref(R),
-                          C.byref(L) if L is not None else None, device, stream), "pp_rollout")
+    _check(entry(m.handle, _ref(b), _ref(T), _ref(prm), _ref(cfg), _ref(R), _ref(L), device, stream,
+                 *[_ref(x) for x in stages]), what)
+
+
+def _judge_stage(judge, jcfg):
+    """(configuration, state structure) of a rollout's optional judge; a judge without a
+    configuration gets the default one."""
+    if judge is None:
+        return jcfg, None
+    return jcfg if jcfg is not None else default_judge_cfg(), judge_struct(judge)
 
 
 def default_judge_cfg(**over) -> JudgeCfg:
     """pp_judge_cfg_default, with fields overridden by keyword."""
-    c = JudgeCfg()
-    lib.pp_judge_cfg_default(C.byref(c))
-    for k, v in over.items():
-        if k not in dict(JudgeCfg._fields_):
-            raise KeyError(k)
-        setattr(c, k, v)
-    return c
+    return _default_cfg(JudgeCfg, lib.pp_judge_cfg_default, over)
 
 
 def alloc_judge(S, xp="numpy", device=None):
     """Zero-filled judge state of S scenes (every scene a fresh episode)."""
-    if xp == "numpy":
-        mk = lambda sh, dt: np.zeros(sh, dt)
-    else:
-        import torch
-        tdt = {"f8": torch.float64, "i4": torch.int32, "u4": torch.int32}
-        mk = lambda sh, dt: torch.zeros(sh, dtype=tdt[dt], device=device)
-    return {k: mk((S,) if lead is None else (lead, S), dt) for k, dt, lead in JUDGE_FIELDS}
+    return _alloc_state(JUDGE_FIELDS, S, None, xp, device)
 
 
 def judge_struct(j) -> Judge:
-    J = Judge()
-    for k, _, _ in JUDGE_FIELDS:
-        setattr(J, k, _ptr(j[k]))
-    return J
+    return _struct(Judge, [k for k, _, _ in JUDGE_FIELDS], j)
 
 
 def judge_to_numpy(j):
-    out = {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in j.items()}
+    out = _to_numpy(j)
     out["flags"] = out["flags"].view(np.uint32)
     return out
 
@@ -661,56 +674,36 @@ def judge_frame(m, scenes, traffic, result, judge, consume=3, cfg=None, host=Non
     cfg = cfg if cfg is not None else default_judge_cfg()
     b, T, R, J = scene_struct(scenes), traffic_struct(traffic), result_struct(result), judge_struct(judge)
     if host:
-        _check(lib.pp_judge_frame_host(m.handle, C.byref(b), C.byref(T), C.byref(R), consume, C.byref(cfg),
-                                       C.byref(J)), "pp_judge_frame_host")
+        _check(lib.pp_judge_frame_host(m.handle, _ref(b), _ref(T), _ref(R), consume, _ref(cfg), _ref(J)),
+               "pp_judge_frame_host")
     else:
-        _check(lib.pp_judge_frame(m.handle, C.byref(b), C.byref(T), C.byref(R), consume, C.byref(cfg),
-                                  C.byref(J), device, stream), "pp_judge_frame")
+        _check(lib.pp_judge_frame(m.handle, _ref(b), _ref(T), _ref(R), consume, _ref(cfg), _ref(J), device, stream),
+               "pp_judge_frame")
 
 
 def rollout_judged(m, scenes, traffic, prm, result, judge, n_frames, consume=3, sensor_range=300.0, log=None,
                    cfg=None, device=0, stream=None):
     """pp_rollout_judged: rollout() with the judge run on every frame; `judge` updated in place."""
-    b, T, R, J = scene_struct(scenes), traffic_struct(traffic), result_struct(result), judge_struct(judge)
-    rc = RolloutCfg(n_frames, consume, float(sensor_range))
-    cfg = cfg if cfg is not None else default_judge_cfg()
-    L = log_struct(log) if log is not None else None
-    _check(lib.pp_rollout_judged(m.handle, C.byref(b), C.byref(T), C.byref(prm), C.byref(rc), C.byref(R),
-                                 C.byref(L) if L is not None else None, device, stream, C.byref(cfg),
-                                 C.byref(J)), "pp_rollout_judged")
+    _rollout(lib.pp_rollout_judged, "pp_rollout_judged", m, scenes, traffic, prm, result, n_frames, consume,
+             sensor_range, log, device, stream, cfg if cfg is not None else default_judge_cfg(), judge_struct(judge))
 
 
 def default_follow_cfg(**over) -> FollowCfg:
     """pp_follow_cfg_default, with fields overridden by keyword."""
-    c = FollowCfg()
-    lib.pp_follow_cfg_default(C.byref(c))
-    for k, v in over.items():
-        if k not in dict(FollowCfg._fields_):
-            raise KeyError(k)
-        setattr(c, k, v)
-    return c
+    return _default_cfg(FollowCfg, lib.pp_follow_cfg_default, over)
 
 
 def alloc_follow(S, n=12, xp="numpy", device=None):
     """Zero-filled follow state of S scenes x n cars (every scene a fresh episode)."""
-    if xp == "numpy":
-        mk = lambda sh, dt: np.zeros(sh, dt)
-    else:
-        import torch
-        tdt = {"f8": torch.float64, "i4": torch.int32}
-        mk = lambda sh, dt: torch.zeros(sh, dtype=tdt[dt], device=device)
-    return {k: mk((n, S) if per_car else (S,), dt) for k, dt, per_car in FOLLOW_FIELDS}
+    return _alloc_state(FOLLOW_FIELDS, S, n, xp, device)
 
 
 def follow_struct(f) -> Follow:
-    F = Follow()
-    for k, _, _ in FOLLOW_FIELDS:
-        setattr(F, k, _ptr(f[k]))
-    return F
+    return _struct(Follow, [k for k, _, _ in FOLLOW_FIELDS], f)
 
 
 def follow_to_numpy(f):
-    return {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in f.items()}
+    return _to_numpy(f)
 
 
 def traffic_follow(m, scenes, traffic, follow, consume=3, cfg=None, host=None, device=0, stream=None):
@@ -723,11 +716,11 @@ def traffic_follow(m, scenes, traffic, follow, consume=3, cfg=None, host=None, d
     assert follow["desired"].shape[0] >= int(traffic["n_cars"]), "follow state holds fewer cars than the traffic"
     b, T, F = scene_struct(scenes), traffic_struct(traffic), follow_struct(follow)
     if host:
-        _check(lib.pp_traffic_follow_host(m.handle, C.byref(b), C.byref(T), consume, C.byref(cfg), C.byref(F)),
+        _check(lib.pp_traffic_follow_host(m.handle, _ref(b), _ref(T), consume, _ref(cfg), _ref(F)),
                "pp_traffic_follow_host")
     else:
-        _check(lib.pp_traffic_follow(m.handle, C.byref(b), C.byref(T), consume, C.byref(cfg), C.byref(F), device,
-                                     stream), "pp_traffic_follow")
+        _check(lib.pp_traffic_follow(m.handle, _ref(b), _ref(T), consume, _ref(cfg), _ref(F), device, stream),
+               "pp_traffic_follow")
 
 
 def rollout_reactive(m, scenes, traffic, prm, result, follow, n_frames, consume=3, sensor_range=300.0, log=None,
@@ -735,51 +728,27 @@ def rollout_reactive(m, scenes, traffic, prm, result, follow, n_frames, consume=
     """pp_rollout_reactive: rollout() whose traffic follows the vehicle ahead (follow state updated in
     place), judged on every frame when `judge` is given."""
     assert follow["desired"].shape[0] >= int(traffic["n_cars"]), "follow state holds fewer cars than the traffic"
-    b, T, R, F = scene_struct(scenes), traffic_struct(traffic), result_struct(result), follow_struct(follow)
-    rc = RolloutCfg(n_frames, consume, float(sensor_range))
-    fcfg = fcfg if fcfg is not None else default_follow_cfg()
-    J = judge_struct(judge) if judge is not None else None
-    if judge is not None and jcfg is None:
-        jcfg = default_judge_cfg()
-    L = log_struct(log) if log is not None else None
-    _check(lib.pp_rollout_reactive(m.handle, C.byref(b), C.byref(T), C.byref(prm), C.byref(rc), C.byref(R),
-                                   C.byref(L) if L is not None else None, device, stream,
-                                   C.byref(jcfg) if jcfg is not None else None,
-                                   C.byref(J) if J is not None else None, C.byref(fcfg), C.byref(F)),
-           "pp_rollout_reactive")
+    _rollout(lib.pp_rollout_reactive, "pp_rollout_reactive", m, scenes, traffic, prm, result, n_frames, consume,
+             sensor_range, log, device, stream, *_judge_stage(judge, jcfg),
+             fcfg if fcfg is not None else default_follow_cfg(), follow_struct(follow))
 
 
 def default_lane_change_cfg(**over) -> LaneChangeCfg:
     """pp_lane_change_cfg_default, with fields overridden by keyword."""
-    c = LaneChangeCfg()
-    lib.pp_lane_change_cfg_default(C.byref(c))
-    for k, v in over.items():
-        if k not in dict(LaneChangeCfg._fields_):
-            raise KeyError(k)
-        setattr(c, k, v)
-    return c
+    return _default_cfg(LaneChangeCfg, lib.pp_lane_change_cfg_default, over)
 
 
 def alloc_lane_change(S, n=12, xp="numpy", device=None):
     """Zero-filled lane-change state of S scenes x n cars (every scene a fresh episode)."""
-    if xp == "numpy":
-        mk = lambda sh, dt: np.zeros(sh, dt)
-    else:
-        import torch
-        tdt = {"f8": torch.float64, "i4": torch.int32}
-        mk = lambda sh, dt: torch.zeros(sh, dtype=tdt[dt], device=device)
-    return {k: mk((n, S) if per_car else (S,), dt) for k, dt, per_car in LANE_CHANGE_FIELDS}
+    return _alloc_state(LANE_CHANGE_FIELDS, S, n, xp, device)
 
 
 def lane_change_struct(l) -> LaneChange:
-    L = LaneChange()
-    for k, _, _ in LANE_CHANGE_FIELDS:
-        setattr(L, k, _ptr(l[k]))
-    return L
+    return _struct(LaneChange, [k for k, _, _ in LANE_CHANGE_FIELDS], l)
 
 
 def lane_change_to_numpy(l):
-    return {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in l.items()}
+    return _to_numpy(l)
 
 
 def traffic_lane_change(m, scenes, traffic, follow, lane_change, consume=3, fcfg=None, cfg=None, host=None,
@@ -796,11 +765,11 @@ def traffic_lane_change(m, scenes, traffic, follow, lane_change, consume=3, fcfg
     assert lane_change["home"].shape[0] >= n, "lane-change state holds fewer cars than the traffic"
     b, T, F, L = scene_struct(scenes), traffic_struct(traffic), follow_struct(follow), lane_change_struct(lane_change)
     if host:
-        _check(lib.pp_traffic_lane_change_host(m.handle, C.byref(b), C.byref(T), consume, C.byref(fcfg), C.byref(F),
-                                               C.byref(cfg), C.byref(L)), "pp_traffic_lane_change_host")
+        _check(lib.pp_traffic_lane_change_host(m.handle, _ref(b), _ref(T), consume, _ref(fcfg), _ref(F), _ref(cfg),
+                                               _ref(L)), "pp_traffic_lane_change_host")
     else:
-        _check(lib.pp_traffic_lane_change(m.handle, C.byref(b), C.byref(T), consume, C.byref(fcfg), C.byref(F),
-                                          C.byref(cfg), C.byref(L), device, stream), "pp_traffic_lane_change")
+        _check(lib.pp_traffic_lane_change(m.handle, _ref(b), _ref(T), consume, _ref(fcfg), _ref(F), _ref(cfg),
+                                          _ref(L), device, stream), "pp_traffic_lane_change")
 
 
 def rollout_lane_changing(m, scenes, traffic, prm, result, follow, lane_change, n_frames, consume=3,
@@ -810,24 +779,13 @@ def rollout_lane_changing(m, scenes, traffic, prm, result, follow, lane_change, 
     updated in place); lane_change=None: exactly rollout_reactive()."""
     n = int(traffic["n_cars"])
     assert follow["desired"].shape[0] >= n, "follow state holds fewer cars than the traffic"
-    b, T, R, F = scene_struct(scenes), traffic_struct(traffic), result_struct(result), follow_struct(follow)
-    rc = RolloutCfg(n_frames, consume, float(sensor_range))
-    fcfg = fcfg if fcfg is not None else default_follow_cfg()
-    J = judge_struct(judge) if judge is not None else None
-    if judge is not None and jcfg is None:
-        jcfg = default_judge_cfg()
-    LS = None
+    change = (None, None)         # (no lane-change state: no configuration either, whatever lcfg is)
     if lane_change is not None:
         assert lane_change["home"].shape[0] >= n, "lane-change state holds fewer cars than the traffic"
-        LS = lane_change_struct(lane_change)
-        lcfg = lcfg if lcfg is not None else default_lane_change_cfg()
-    L = log_struct(log) if log is not None else None
-    _check(lib.pp_rollout_lane_changing(m.handle, C.byref(b), C.byref(T), C.byref(prm), C.byref(rc), C.byref(R),
-                                        C.byref(L) if L is not None else None, device, stream,
-                                        C.byref(jcfg) if jcfg is not None else None,
-                                        C.byref(J) if J is not None else None, C.byref(fcfg), C.byref(F),
-                                        C.byref(lcfg) if LS is not None else None,
-                                        C.byref(LS) if LS is not None else None), "pp_rollout_lane_changing")
+        change = (lcfg if lcfg is not None else default_lane_change_cfg(), lane_change_struct(lane_change))
+    _rollout(lib.pp_rollout_lane_changing, "pp_rollout_lane_changing", m, scenes, traffic, prm, result, n_frames,
+             consume, sensor_range, log, device, stream, *_judge_stage(judge, jcfg),
+             fcfg if fcfg is not None else default_follow_cfg(), follow_struct(follow), *change)
 
 
 def plan_reset(m, device=0):
@@ -835,7 +793,7 @@ def plan_reset(m, device=0):
 
 
 def scenes_to_numpy(d):
-    return {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in d.items()}
+    return _to_numpy(d)
 
 
 def synth_host(m: Map, S, seed=0x5EED0001, first=0, car_stride=12):
@@ -857,21 +815,15 @@ def alloc_result(S, prm: Params, xp="numpy", device=None, info=False):
     D = max(prm.n_draws, 1)
     Cn = D * NUM_LANES * prm.n_speeds
     N = prm.n_points
-    if xp == "numpy":
-        mk = lambda sh, dt: np.zeros(sh, dt)
-        f8, i4, u4 = np.float64, np.int32, np.uint32
-    else:
-        import torch
-        mk = lambda sh, dt: torch.zeros(sh, dtype=dt, device=device)
-        f8, i4, u4 = torch.float64, torch.int32, torch.int32
+    mk = _zeros(xp, device)
     # next_x/next_y are point-major [N][S] (include/pp.h)
-    r = {"winner": mk((S,), i4), "n_out": mk((S,), i4), "next_x": mk((N, S), f8),
-         "next_y": mk((N, S), f8), "cost": mk((S, Cn), f8), "status": mk((S,), u4)}
+    r = {"winner": mk((S,), "i4"), "n_out": mk((S,), "i4"), "next_x": mk((N, S), "f8"),
+         "next_y": mk((N, S), "f8"), "cost": mk((S, Cn), "f8"), "status": mk((S,), "u4")}
     if prm.emit_paths:
-        r["paths"] = mk((S, N, Cn, 2), f8)
-        r["path_len"] = mk((S, Cn), i4)
+        r["paths"] = mk((S, N, Cn, 2), "f8")
+        r["path_len"] = mk((S, Cn), "i4")
     if D > 1:
-        r["draw_mean_cost"] = mk((S, NUM_LANES * prm.n_speeds), f8)
+        r["draw_mean_cost"] = mk((S, NUM_LANES * prm.n_speeds), "f8")
     if info:
         if xp == "numpy":
             r["info"] = np.zeros((S,), INFO_DTYPE)
@@ -882,11 +834,8 @@ def alloc_result(S, prm: Params, xp="numpy", device=None, info=False):
 
 
 def result_struct(r) -> Result:
-    R = Result()
-    for k in ["winner", "n_out", "next_x", "next_y", "cost", "status", "paths", "path_len", "info",
-              "draw_mean_cost"]:
-        setattr(R, k, _ptr(r.get(k)))
-    return R
+    return _struct(Result, ["winner", "n_out", "next_x", "next_y", "cost", "status", "paths", "path_len", "info",
+                            "draw_mean_cost"], r, optional=True)
 
 
 def result_to_numpy(r):

@@ -1,7 +1,7 @@
 // episode_host.cpp — the episode generator's shared arithmetic (csrc/pp_episode.h, the function
 // k_synth_episode and pp_synth_episode_host both call) as a stand-alone host program under
 // AddressSanitizer and UndefinedBehaviorSanitizer (`make -C carnd-path-planning-project_amd
-// sanitize-episode`, driven by tests/test_episode_sanitize.py). Test infrastructure; never part of
+// sanitize-episode`, driven by tests/test_world_sanitize.py). Test infrastructure; never part of
 // the product library.
 //
 // Every array is a std::vector of exactly the size include/pp.h states, so an index outside
@@ -12,76 +12,14 @@
 //   random       seeded configurations inside ring_ok's bound: 0..20 cars, egos at rest, parked cars,
 //                no table, no states, any scene count; shards concatenate
 // Exit 0 and a last line "clean" when every check passed; a sanitizer report aborts the process.
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
 #include <algorithm>
-#include <vector>
 
-#define PP_HD
-#include "../../include/pp.h"
-#include "../../carnd-path-planning-project_amd/csrc/pp_synth.h"
-#include "../../carnd-path-planning-project_amd/csrc/pp_follow.h"
+#include "world_fixture.h"
 #include "../../carnd-path-planning-project_amd/csrc/pp_episode.h"
 
 namespace {
 
-int g_fail = 0;
-#define CHECK(c)                                                                  \
-    do {                                                                          \
-        if (!(c)) { fprintf(stderr, "CHECK failed %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-    } while (0)
-
-struct Rng {                      // xorshift64*: seeded, reproducible
-    uint64_t s;
-    explicit Rng(uint64_t seed) : s(seed * 0x9E3779B97F4A7C15ull + 1) {}
-    uint64_t next() { s ^= s >> 12; s ^= s << 25; s ^= s >> 27; return s * 0x2545F4914F6CDD1Dull; }
-    int below(int n) { return n > 0 ? (int)(next() % (uint64_t)n) : 0; }
-    double unit() { return (double)(next() >> 11) * (1.0 / 9007199254740992.0); }
-    double uni(double lo, double hi) { return lo + (hi - lo) * unit(); }
-};
-
-constexpr int kWp = 64;
-constexpr int NL = PP_NUM_LANES;
-constexpr double kPi = 3.14159265358979323846;
-
-// lane tables of a ring of kWp waypoints, radius 900 m (about 5.7 km round), driven counter-clockwise:
-// lane r's centre 4 (r + 0.5) m to the right of the waypoints (outside); and their arc prefix
-struct Ring {
-    std::vector<double> t, arc;
-    ppsynth::LaneTables T;
-    ppfollow::ArcTables A;
-    double min_loop;
-    Ring() : t((size_t)5 * NL * kWp), arc(ppfollow::arc_doubles(kWp)) {
-        double* lx = t.data();
-        double* ly = lx + NL * kWp;
-        double* sl = ly + NL * kWp;
-        double* tx = sl + NL * kWp;
-        double* ty = tx + NL * kWp;
-        for (int l = 0; l < NL; l++)
-            for (int i = 0; i < kWp; i++) {
-                const double r = 900.0 + 4.0 * (l + 0.5), a = 2 * kPi * i / kWp;
-                lx[l * kWp + i] = r * cos(a);
-                ly[l * kWp + i] = r * sin(a);
-            }
-        for (int l = 0; l < NL; l++)
-            for (int i = 0; i < kWp; i++) {
-                const int p = i == 0 ? kWp - 1 : i - 1;
-                const double dx = lx[l * kWp + i] - lx[l * kWp + p], dy = ly[l * kWp + i] - ly[l * kWp + p];
-                const double len = sqrt(dx * dx + dy * dy);
-                sl[l * kWp + i] = len;
-                tx[l * kWp + i] = dx / len;
-                ty[l * kWp + i] = dy / len;
-            }
-        T.n = kWp; T.lc_x = lx; T.lc_y = ly; T.seg_len = sl; T.tan_x = tx; T.tan_y = ty;
-        ppfollow::build_arc(sl, kWp, arc.data());
-        A = ppfollow::arc_tables(arc.data(), kWp);
-        min_loop = A.loop[0];
-        for (int l = 1; l < NL; l++) min_loop = std::min(min_loop, A.loop[l]);
-    }
-};
+constexpr int kWp = 64;           // radius 900 m: about 5.7 km round
 
 struct Scenes {                   // pp_scene_batch's written arrays over exactly sized vectors
     int64_t S;
@@ -103,67 +41,8 @@ struct Scenes {                   // pp_scene_batch's written arrays over exactl
     }
 };
 
-struct Traffic {
-    int64_t S;
-    int n;
-    std::vector<int32_t> lane, seg;
-    std::vector<double> t, off, v;
-    Traffic(int64_t S_, int n_) : S(S_), n(n_), lane(S_ * n_), seg(S_ * n_), t(S_ * n_), off(S_ * n_), v(S_ * n_) {}
-    ppsynth::TrafficV view() {
-        ppsynth::TrafficV tv;
-        tv.S = S; tv.n = n; tv.lane = lane.data(); tv.seg = seg.data(); tv.t = t.data(); tv.off = off.data(); tv.v = v.data();
-        return tv;
-    }
-};
-
-struct JudgeState {               // pp_judge over exactly sized vectors, filled with junk
-    std::vector<int32_t> steps, count, first_step, first_car, seg_hint, off_run;
-    std::vector<uint32_t> flags;
-    std::vector<double> head_x, head_y, ring_vx, ring_vy, dist, clean, min_sep, max_mph, max_acc, max_jerk;
-    explicit JudgeState(int64_t S)
-        : steps(S, 9), count(S * PP_INC_KINDS, 9), first_step(S * PP_INC_KINDS, 9), first_car(S, 9), seg_hint(S, 9),
-          off_run(S, 9), flags(S, 9u), head_x(S, 9), head_y(S, 9), ring_vx(S * PP_JUDGE_RING, 9),
-          ring_vy(S * PP_JUDGE_RING, 9), dist(S, 9), clean(S, 9), min_sep(S, 9), max_mph(S, 9), max_acc(S, 9),
-          max_jerk(S, 9) {}
-    pp_judge view() {
-        pp_judge j;
-        j.steps = steps.data(); j.flags = flags.data(); j.count = count.data(); j.first_step = first_step.data();
-        j.first_car = first_car.data(); j.seg_hint = seg_hint.data(); j.off_run = off_run.data();
-        j.head_x = head_x.data(); j.head_y = head_y.data(); j.ring_vx = ring_vx.data(); j.ring_vy = ring_vy.data();
-        j.dist = dist.data(); j.clean_dist = clean.data(); j.min_sep = min_sep.data(); j.max_speed_mph = max_mph.data();
-        j.max_acc = max_acc.data(); j.max_jerk = max_jerk.data();
-        return j;
-    }
-};
-
-struct FollowState {
-    std::vector<int32_t> started, ego_seg, leader;
-    std::vector<double> desired, next_speed, gap;
-    FollowState(int64_t S, int n)
-        : started(S, 1), ego_seg(S, 5), leader(S * n), desired(S * n), next_speed(S * n), gap(S * n) {}
-    pp_follow view() {
-        pp_follow f;
-        f.started = started.data(); f.ego_seg = ego_seg.data(); f.desired = desired.data();
-        f.next_speed = next_speed.data(); f.leader = leader.data(); f.gap = gap.data();
-        return f;
-    }
-};
-
-pp_follow_cfg default_gap() {     // include/pp.h pp_follow_cfg_default
-    pp_follow_cfg c;
-    memset(&c, 0, sizeof(c));
-    c.max_acc = 2.0; c.comfort_brake = 3.0; c.max_brake = 8.0; c.time_headway = 1.2; c.min_gap = 2.0;
-    c.gap_floor = 0.5; c.horizon = 150; c.car_length = c.ego_length = 4.5; c.lateral_reach = 2.0; c.react_to_ego = 1;
-    return c;
-}
-
-pp_episode_cfg default_cfg() {    // include/pp.h pp_episode_cfg_default
-    pp_episode_cfg c;
-    memset(&c, 0, sizeof(c));
-    c.n_cars = 12; c.ego_speed_max = 20; c.car_speed_min = 5; c.car_speed_max = 25; c.ahead_share = 0.75;
-    c.extra_gap = 40; c.offset_jitter = 0.3; c.gap_slack = 1e-6;
-    return c;
-}
+pp_follow_cfg default_gap() { return default_of(ppfollow::cfg_default); }
+pp_episode_cfg default_cfg() { return default_of(ppepisode::cfg_default); }
 
 void generate(const Ring& R, uint64_t seed, int64_t first, const pp_episode_cfg& cfg, const pp_follow_cfg& gap,
               Scenes& sc, bool table, Traffic& tr, JudgeState* js, FollowState* fs) {
@@ -231,7 +110,7 @@ void check_states(const Ring& R, const Scenes& sc, const JudgeState& js, const F
         const double ux = R.T.tan_x[lane * kWp + seg], uy = R.T.tan_y[lane * kWp + seg], ve = sc.mph[s] / 2.237;
         CHECK(js.steps[s] == PP_JUDGE_RING && js.flags[s] == 0 && js.first_car[s] == 0 && js.off_run[s] == 0);
         CHECK(js.head_x[s] == ux && js.head_y[s] == uy && isinf(js.min_sep[s]) && js.min_sep[s] > 0);
-        CHECK(js.dist[s] == 0 && js.clean[s] == 0 && js.max_mph[s] == 0 && js.max_acc[s] == 0 && js.max_jerk[s] == 0);
+        CHECK(js.dist[s] == 0 && js.clean_dist[s] == 0 && js.max_speed_mph[s] == 0 && js.max_acc[s] == 0 && js.max_jerk[s] == 0);
         for (int k = 0; k < PP_INC_KINDS; k++) CHECK(js.count[k * S + s] == 0 && js.first_step[k * S + s] == 0);
         for (int k = 0; k < PP_JUDGE_RING; k++)
             CHECK(fabs(js.ring_vx[k * S + s] - ve * ux) < 1e-12 && fabs(js.ring_vy[k * S + s] - ve * uy) < 1e-12);
@@ -252,8 +131,8 @@ void defaults(const Ring& R) {
     CHECK(ppepisode::cfg_ok(cfg) && ppepisode::ring_ok(cfg, gap, R.min_loop));
     Scenes sc(S, 12, 12);
     Traffic tr(S, 12);
-    JudgeState js(S);
-    FollowState fs(S, 12);
+    JudgeState js(S, 9);
+    FollowState fs(S, 12, 1, 5);
     generate(R, 7, 0, cfg, gap, sc, true, tr, &js, &fs);
     check_states(R, sc, js, fs);
     for (int64_t s = 0; s < S; s++) {
@@ -270,8 +149,7 @@ void defaults(const Ring& R) {
 
     // one follow update from the start: nobody brakes harder than max_acc
     const std::vector<double> before = tr.v;
-    FollowState f2(S, 12);
-    std::fill(f2.started.begin(), f2.started.end(), 0);
+    FollowState f2(S, 12, 0, 5);
     const pp_follow fv = f2.view();
     const ppsynth::TrafficV tv = tr.view();
     double worst = 0;
@@ -322,8 +200,8 @@ void random_configs(const Ring& R, uint64_t seed, int rounds) {
         const bool table = g.below(3) != 0, states = g.below(3) != 0;
         Scenes sc(S, n, n + g.below(3));
         Traffic tr(S, n);
-        JudgeState js(S);
-        FollowState fs(S, n);
+        JudgeState js(S, 9);
+        FollowState fs(S, n, 1, 5);
         generate(R, g.next(), (int64_t)(g.next() >> 20), cfg, gap, sc, table, tr, &js, states ? &fs : nullptr);
         for (int64_t s = 0; s < S; s++) {
             CHECK(sc.n_cars[s] == n);
@@ -349,7 +227,7 @@ int main() {
     bad = default_cfg();
     bad.extra_gap = NAN;
     CHECK(!ppepisode::cfg_ok(bad));
-    const Ring R;
+    const Ring R(kWp, 900.0);
     bad = default_cfg();
     bad.n_cars = 200;
     CHECK(ppepisode::cfg_ok(bad) && !ppepisode::ring_ok(bad, default_gap(), R.min_loop));

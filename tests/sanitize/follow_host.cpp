@@ -1,7 +1,7 @@
 // follow_host.cpp — reactive traffic's shared arithmetic (csrc/pp_follow.h, the function k_follow and
 // pp_traffic_follow_host both call) as a stand-alone host program under AddressSanitizer and
 // UndefinedBehaviorSanitizer (`make -C carnd-path-planning-project_amd sanitize-follow`, driven by
-// tests/test_follow_sanitize.py). Test infrastructure; never part of the product library.
+// tests/test_world_sanitize.py). Test infrastructure; never part of the product library.
 //
 // Every array is a std::vector of exactly the size include/pp.h states, so an index outside
 // [k * S + s] is a heap overflow the sanitizer reports. On lane tables of a 16-waypoint ring:
@@ -11,126 +11,19 @@
 //                the ego anywhere (on a lane, between lanes, far off), any consume, random valid
 //                configurations, states reused by zeroing `started`
 // Exit 0 and a last line "clean" when every check passed; a sanitizer report aborts the process.
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-
-#define PP_HD
-#include "../../include/pp.h"
-#include "../../carnd-path-planning-project_amd/csrc/pp_synth.h"
-#include "../../carnd-path-planning-project_amd/csrc/pp_follow.h"
+#include "world_fixture.h"
 
 namespace {
 
-int g_fail = 0;
-#define CHECK(c)                                                                  \
-    do {                                                                          \
-        if (!(c)) { fprintf(stderr, "CHECK failed %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-    } while (0)
-
-struct Rng {                      // xorshift64*: seeded, reproducible
-    uint64_t s;
-    explicit Rng(uint64_t seed) : s(seed * 0x9E3779B97F4A7C15ull + 1) {}
-    uint64_t next() { s ^= s >> 12; s ^= s << 25; s ^= s >> 27; return s * 0x2545F4914F6CDD1Dull; }
-    int below(int n) { return n > 0 ? (int)(next() % (uint64_t)n) : 0; }
-    double unit() { return (double)(next() >> 11) * (1.0 / 9007199254740992.0); }
-    double uni(double lo, double hi) { return lo + (hi - lo) * unit(); }
-};
-
 constexpr int kWp = 16;
-constexpr int NL = PP_NUM_LANES;
-constexpr double kPi = 3.14159265358979323846;
 
-// lane tables of a ring of kWp waypoints, radius 120 m, driven counter-clockwise: lane r's centre
-// 4 (r + 0.5) m to the right of the waypoints (outside); and their arc prefix
-struct Ring {
-    std::vector<double> t, arc;
-    ppsynth::LaneTables T;
-    ppfollow::ArcTables A;
-    Ring() : t((size_t)5 * NL * kWp), arc(ppfollow::arc_doubles(kWp)) {
-        double* lx = t.data();
-        double* ly = lx + NL * kWp;
-        double* sl = ly + NL * kWp;
-        double* tx = sl + NL * kWp;
-        double* ty = tx + NL * kWp;
-        for (int l = 0; l < NL; l++)
-            for (int i = 0; i < kWp; i++) {
-                const double r = 120.0 + 4.0 * (l + 0.5), a = 2 * kPi * i / kWp;
-                lx[l * kWp + i] = r * cos(a);
-                ly[l * kWp + i] = r * sin(a);
-            }
-        for (int l = 0; l < NL; l++)
-            for (int i = 0; i < kWp; i++) {
-                const int p = i == 0 ? kWp - 1 : i - 1;
-                const double dx = lx[l * kWp + i] - lx[l * kWp + p], dy = ly[l * kWp + i] - ly[l * kWp + p];
-                const double len = sqrt(dx * dx + dy * dy);
-                sl[l * kWp + i] = len;
-                tx[l * kWp + i] = dx / len;
-                ty[l * kWp + i] = dy / len;
-            }
-        T.n = kWp; T.lc_x = lx; T.lc_y = ly; T.seg_len = sl; T.tan_x = tx; T.tan_y = ty;
-        ppfollow::build_arc(sl, kWp, arc.data());
-        A = ppfollow::arc_tables(arc.data(), kWp);
-    }
-    // the point t of the way along segment seg of lane l, lat metres to the right
-    void point(int l, int seg, double t, double lat, double* x, double* y) const {
-        const int p = seg == 0 ? kWp - 1 : seg - 1;
-        const double ax = T.lc_x[l * kWp + p], ay = T.lc_y[l * kWp + p];
-        const double ux = T.tan_x[l * kWp + seg], uy = T.tan_y[l * kWp + seg];
-        *x = ax + (T.lc_x[l * kWp + seg] - ax) * t + uy * lat;
-        *y = ay + (T.lc_y[l * kWp + seg] - ay) * t - ux * lat;
-    }
-};
-
-struct State {                    // pp_follow over exactly sized vectors
-    int64_t S;
-    int n;
-    std::vector<int32_t> started, ego_seg, leader;
-    std::vector<double> desired, next_speed, gap;
-    State(int64_t S_, int n_)
-        : S(S_), n(n_), started(S_), ego_seg(S_), leader(S_ * n_), desired(S_ * n_), next_speed(S_ * n_), gap(S_ * n_) {}
-    pp_follow view() {
-        pp_follow f;
-        f.started = started.data(); f.ego_seg = ego_seg.data(); f.desired = desired.data();
-        f.next_speed = next_speed.data(); f.leader = leader.data(); f.gap = gap.data();
-        return f;
-    }
-};
-
-struct Traffic {
-    int64_t S;
-    int n;
-    std::vector<int32_t> lane, seg;
-    std::vector<double> t, off, v;
-    Traffic(int64_t S_, int n_) : S(S_), n(n_), lane(S_ * n_), seg(S_ * n_), t(S_ * n_), off(S_ * n_), v(S_ * n_) {}
-    ppsynth::TrafficV view() {
-        ppsynth::TrafficV tv;
-        tv.S = S; tv.n = n; tv.lane = lane.data(); tv.seg = seg.data(); tv.t = t.data(); tv.off = off.data(); tv.v = v.data();
-        return tv;
-    }
-};
-
-pp_follow_cfg default_cfg() {     // include/pp.h pp_follow_cfg_default
-    pp_follow_cfg c;
-    memset(&c, 0, sizeof(c));
-    c.max_acc = 2.0; c.comfort_brake = 3.0; c.max_brake = 8.0; c.time_headway = 1.2; c.min_gap = 2.0;
-    c.gap_floor = 0.5; c.horizon = 150; c.car_length = c.ego_length = 4.5; c.lateral_reach = 2.0; c.react_to_ego = 1;
-    return c;
-}
+pp_follow_cfg default_cfg() { return default_of(ppfollow::cfg_default); }
 
 void follow(const Ring& R, const std::vector<double>& ex, const std::vector<double>& ey, const std::vector<double>& mph,
-            Traffic& tr, int consume, const pp_follow_cfg& cfg, State& st) {
+            Traffic& tr, int consume, const pp_follow_cfg& cfg, FollowState& st) {
     const pp_follow f = st.view();
     const ppsynth::TrafficV tv = tr.view();
     for (int64_t s = 0; s < tr.S; s++) ppfollow::follow_scene(R.T, R.A, tr.S, s, ex[s], ey[s], mph[s], tv, consume, cfg, f);
-}
-
-void move(const Ring& R, Traffic& tr, int consume) {
-    for (size_t k = 0; k < tr.lane.size(); k++)
-        ppsynth::lane_advance(R.T, tr.lane[k], &tr.seg[k], &tr.t[k], tr.v[k] * 0.02 * consume);
 }
 
 void platoon(const Ring& R) {
@@ -148,7 +41,7 @@ void platoon(const Ring& R) {
         }
         R.point(1, 2, 40.0 / L, 0.3, &ex[s], &ey[s]);
     }
-    State st(S, 3);
+    FollowState st(S, 3);
     follow(R, ex, ey, mph, tr, 3, cfg, st);
     for (int64_t s = 0; s < S; s++) {
         CHECK(st.leader[0 * S + s] == 2 && st.leader[1 * S + s] == 0 && st.leader[2 * S + s] == 3);   // 3 = the ego
@@ -177,7 +70,7 @@ void free_road(const Ring& R) {
         R.point(NL - 1, 3, 0.5, 3.0, &ex[s], &ey[s]);   // 3 m outside the outermost lane
     }
     const std::vector<double> v0 = tr.v;
-    State st(S, 12);
+    FollowState st(S, 12);
     for (int f = 0; f < 50; f++) { follow(R, ex, ey, mph, tr, 3, cfg, st); move(R, tr, 3); }
     CHECK(memcmp(v0.data(), tr.v.data(), v0.size() * sizeof(double)) == 0);
     for (size_t k = 0; k < st.leader.size(); k++) CHECK(st.leader[k] == -1 && isinf(st.gap[k]));
@@ -202,7 +95,7 @@ void random_frames(const Ring& R, uint64_t seed, int rounds) {
             tr.off[k] = g.uni(-1, 1); tr.v[k] = g.below(6) ? g.uni(0, 30) : 0.0;
             if (k >= (size_t)S && !g.below(10)) { tr.lane[k] = tr.lane[k - S]; tr.seg[k] = tr.seg[k - S]; tr.t[k] = tr.t[k - S]; }
         }
-        State st(S, n_cars);
+        FollowState st(S, n_cars);
         const int n_frames = 1 + g.below(30);
         std::vector<double> ex(S), ey(S), mph(S);
         for (int64_t s = 0; s < S; s++) R.point(g.below(NL), g.below(kWp), g.unit(), g.uni(-3, 3), &ex[s], &ey[s]);
@@ -251,7 +144,7 @@ int main() {
     bad.horizon = -1;
     CHECK(!ppfollow::cfg_ok(bad));
     CHECK(ppfollow::cfg_ok(default_cfg()));
-    const Ring R;
+    const Ring R(kWp, 120.0);
     platoon(R);
     free_road(R);
     random_frames(R, 20261019, 300);

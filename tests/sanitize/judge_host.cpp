@@ -1,7 +1,7 @@
 // judge_host.cpp — the rollout judge's shared arithmetic (csrc/pp_judge.h, the function k_judge and
 // pp_judge_frame_host both call) as a stand-alone host program under AddressSanitizer and
 // UndefinedBehaviorSanitizer (`make -C carnd-path-planning-project_amd sanitize-judge`, driven by
-// tests/test_judge_sanitize.py). Test infrastructure; never part of the product library.
+// tests/test_world_sanitize.py). Test infrastructure; never part of the product library.
 //
 // Every array is a std::vector of exactly the size include/pp.h states, so an index outside
 // [k * S + s] is a heap overflow the sanitizer reports. On lane tables of a 16-waypoint ring:
@@ -10,124 +10,18 @@
 //   random       seeded frames: any n_out against any consume, 0..20 cars, teleporting plans,
 //                every valid window pair, states reused by zeroing `steps`
 // Exit 0 and a last line "clean" when every check passed; a sanitizer report aborts the process.
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-
-#define PP_HD
-#include "../../include/pp.h"
-#include "../../carnd-path-planning-project_amd/csrc/pp_synth.h"
+#include "world_fixture.h"
 #include "../../carnd-path-planning-project_amd/csrc/pp_judge.h"
 
 namespace {
 
-int g_fail = 0;
-#define CHECK(c)                                                                  \
-    do {                                                                          \
-        if (!(c)) { fprintf(stderr, "CHECK failed %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-    } while (0)
-
-struct Rng {                      // xorshift64*: seeded, reproducible
-    uint64_t s;
-    explicit Rng(uint64_t seed) : s(seed * 0x9E3779B97F4A7C15ull + 1) {}
-    uint64_t next() { s ^= s >> 12; s ^= s << 25; s ^= s >> 27; return s * 0x2545F4914F6CDD1Dull; }
-    int below(int n) { return n > 0 ? (int)(next() % (uint64_t)n) : 0; }
-    double unit() { return (double)(next() >> 11) * (1.0 / 9007199254740992.0); }
-    double uni(double lo, double hi) { return lo + (hi - lo) * unit(); }
-};
-
 constexpr int kWp = 16;
-constexpr int NL = PP_NUM_LANES;
-constexpr double kPi = 3.14159265358979323846;
 
-// lane tables of a ring of kWp waypoints, radius 120 m, driven counter-clockwise: lane r's centre
-// 4 (r + 0.5) m to the right of the waypoints (outside)
-struct Ring {
-    std::vector<double> t;
-    ppsynth::LaneTables T;
-    Ring() : t((size_t)5 * NL * kWp) {
-        double* lx = t.data();
-        double* ly = lx + NL * kWp;
-        double* sl = ly + NL * kWp;
-        double* tx = sl + NL * kWp;
-        double* ty = tx + NL * kWp;
-        for (int l = 0; l < NL; l++)
-            for (int i = 0; i < kWp; i++) {
-                const double r = 120.0 + 4.0 * (l + 0.5), a = 2 * kPi * i / kWp;
-                lx[l * kWp + i] = r * cos(a);
-                ly[l * kWp + i] = r * sin(a);
-            }
-        for (int l = 0; l < NL; l++)
-            for (int i = 0; i < kWp; i++) {
-                const int p = i == 0 ? kWp - 1 : i - 1;
-                const double dx = lx[l * kWp + i] - lx[l * kWp + p], dy = ly[l * kWp + i] - ly[l * kWp + p];
-                const double len = sqrt(dx * dx + dy * dy);
-                sl[l * kWp + i] = len;
-                tx[l * kWp + i] = dx / len;
-                ty[l * kWp + i] = dy / len;
-            }
-        T.n = kWp; T.lc_x = lx; T.lc_y = ly; T.seg_len = sl; T.tan_x = tx; T.tan_y = ty;
-    }
-};
-
-struct State {                    // pp_judge over exactly sized vectors
-    int64_t S;
-    std::vector<int32_t> steps, count, first_step, first_car, seg_hint, off_run;
-    std::vector<uint32_t> flags;
-    std::vector<double> head_x, head_y, ring_vx, ring_vy, dist, clean_dist, min_sep, max_speed_mph, max_acc, max_jerk;
-    explicit State(int64_t S_)
-        : S(S_), steps(S_), count(PP_INC_KINDS * S_), first_step(PP_INC_KINDS * S_), first_car(S_), seg_hint(S_),
-          off_run(S_), flags(S_), head_x(S_), head_y(S_), ring_vx(PP_JUDGE_RING * S_), ring_vy(PP_JUDGE_RING * S_),
-          dist(S_), clean_dist(S_), min_sep(S_), max_speed_mph(S_), max_acc(S_), max_jerk(S_) {}
-    pp_judge view() {
-        pp_judge j;
-        j.steps = steps.data(); j.flags = flags.data(); j.count = count.data(); j.first_step = first_step.data();
-        j.first_car = first_car.data(); j.seg_hint = seg_hint.data(); j.off_run = off_run.data();
-        j.head_x = head_x.data(); j.head_y = head_y.data(); j.ring_vx = ring_vx.data(); j.ring_vy = ring_vy.data();
-        j.dist = dist.data(); j.clean_dist = clean_dist.data(); j.min_sep = min_sep.data();
-        j.max_speed_mph = max_speed_mph.data(); j.max_acc = max_acc.data(); j.max_jerk = max_jerk.data();
-        return j;
-    }
-    template <class V> static bool eq(const V& a, const V& b) {
-        return a.size() == b.size() && memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0;
-    }
-    bool same(const State& o) const {
-        return eq(steps, o.steps) && eq(count, o.count) && eq(first_step, o.first_step) && eq(first_car, o.first_car) &&
-               eq(seg_hint, o.seg_hint) && eq(off_run, o.off_run) && eq(flags, o.flags) && eq(head_x, o.head_x) &&
-               eq(head_y, o.head_y) && eq(ring_vx, o.ring_vx) && eq(ring_vy, o.ring_vy) && eq(dist, o.dist) &&
-               eq(clean_dist, o.clean_dist) && eq(min_sep, o.min_sep) && eq(max_speed_mph, o.max_speed_mph) &&
-               eq(max_acc, o.max_acc) && eq(max_jerk, o.max_jerk);
-    }
-};
-
-struct Traffic {
-    int64_t S;
-    int n;
-    std::vector<int32_t> lane, seg;
-    std::vector<double> t, off, v;
-    Traffic(int64_t S_, int n_) : S(S_), n(n_), lane(S_ * n_), seg(S_ * n_), t(S_ * n_), off(S_ * n_), v(S_ * n_) {}
-    ppsynth::TrafficV view() {
-        ppsynth::TrafficV tv;
-        tv.S = S; tv.n = n; tv.lane = lane.data(); tv.seg = seg.data(); tv.t = t.data(); tv.off = off.data(); tv.v = v.data();
-        return tv;
-    }
-};
-
-pp_judge_cfg default_cfg() {      // include/pp.h pp_judge_cfg_default
-    pp_judge_cfg c;
-    memset(&c, 0, sizeof(c));
-    c.speed_limit_mph = 50; c.max_acc = 10; c.max_jerk = 10;
-    c.ego_length = c.car_length = 4.5; c.ego_width = c.car_width = 2.0;
-    c.lane_tol = 1.0; c.acc_window = 10; c.jerk_window = 50; c.off_lane_steps = 150;
-    return c;
-}
+pp_judge_cfg default_cfg() { return default_of(ppjudge::cfg_default); }
 
 // one call of judge_scene for every scene: ego at point `at` of the track, plan = the next points
 void judge(const Ring& R, int64_t S, const std::vector<double>& px, const std::vector<double>& py, int at, int n_plan,
-           const std::vector<int32_t>& n_out, Traffic& tr, int consume, const pp_judge_cfg& cfg, State& st) {
+           const std::vector<int32_t>& n_out, Traffic& tr, int consume, const pp_judge_cfg& cfg, JudgeState& st) {
     // px/py: [point * S + s]; the plan arrays handed over hold exactly n_plan points
     std::vector<double> nx(px.begin() + (size_t)(at + 1) * S, px.begin() + (size_t)(at + 1 + n_plan) * S);
     std::vector<double> ny(py.begin() + (size_t)(at + 1) * S, py.begin() + (size_t)(at + 1 + n_plan) * S);
@@ -161,7 +55,7 @@ void wrap_and_split(const Ring& R) {
     pp_judge_cfg cfg = default_cfg();
     cfg.off_lane_steps = 40;
     CHECK(ppjudge::cfg_ok(cfg));
-    State a(S), b(S);
+    JudgeState a(S), b(S);
     for (int f = 0; f < steps / 3; f++) judge(R, S, px, py, 3 * f, 3, std::vector<int32_t>(S, 3), tr, 3, cfg, a);
     for (int f = 0; f < steps; f++) judge(R, S, px, py, f, 1, std::vector<int32_t>(S, 1), tr, 1, cfg, b);
     CHECK(a.same(b));
@@ -192,7 +86,7 @@ void random_frames(const Ring& R, uint64_t seed, int rounds) {
             tr.lane[k] = g.below(NL); tr.seg[k] = g.below(kWp); tr.t[k] = g.unit();
             tr.off[k] = g.uni(-1, 1); tr.v[k] = g.uni(0, 3000);                // up to more than a lap per frame
         }
-        State st(S);
+        JudgeState st(S);
         const int n_frames = 1 + g.below(40);
         for (int f = 0; f < n_frames; f++, frames++) {
             const int n_plan = g.below(10), consume = 1 + g.below(9);
@@ -226,7 +120,7 @@ int main() {
     CHECK(!ppjudge::cfg_ok(bad));
     bad.acc_window = 0;
     CHECK(!ppjudge::cfg_ok(bad));
-    const Ring R;
+    const Ring R(kWp, 120.0);
     wrap_and_split(R);
     random_frames(R, 20261019, 300);
     if (g_fail) { fprintf(stderr, "%d checks failed\n", g_fail); return 1; }

@@ -1,7 +1,7 @@
 // lane_change_host.cpp — lane-changing traffic's shared arithmetic (csrc/pp_lanechange.h, the function
 // k_lane_change and pp_traffic_lane_change_host both call) as a stand-alone host program under
 // AddressSanitizer and UndefinedBehaviorSanitizer (`make -C carnd-path-planning-project_amd
-// sanitize-lane-change`, driven by tests/test_lane_change_sanitize.py). Test infrastructure; never part
+// sanitize-lane-change`, driven by tests/test_world_sanitize.py). Test infrastructure; never part
 // of the product library.
 //
 // Every array is a std::vector of exactly the size include/pp.h states, so an index outside
@@ -13,89 +13,12 @@
 //                move per frame, states reused by zeroing `started`, scenes the follow update has not
 //                started
 // Exit 0 and a last line "clean" when every check passed; a sanitizer report aborts the process.
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-
-#define PP_HD
-#include "../../include/pp.h"
-#include "../../carnd-path-planning-project_amd/csrc/pp_synth.h"
-#include "../../carnd-path-planning-project_amd/csrc/pp_follow.h"
+#include "world_fixture.h"
 #include "../../carnd-path-planning-project_amd/csrc/pp_lanechange.h"
 
 namespace {
 
-int g_fail = 0;
-#define CHECK(c)                                                                  \
-    do {                                                                          \
-        if (!(c)) { fprintf(stderr, "CHECK failed %s:%d: %s\n", __FILE__, __LINE__, #c); g_fail++; } \
-    } while (0)
-
-struct Rng {                      // xorshift64*: seeded, reproducible
-    uint64_t s;
-    explicit Rng(uint64_t seed) : s(seed * 0x9E3779B97F4A7C15ull + 1) {}
-    uint64_t next() { s ^= s >> 12; s ^= s << 25; s ^= s >> 27; return s * 0x2545F4914F6CDD1Dull; }
-    int below(int n) { return n > 0 ? (int)(next() % (uint64_t)n) : 0; }
-    double unit() { return (double)(next() >> 11) * (1.0 / 9007199254740992.0); }
-    double uni(double lo, double hi) { return lo + (hi - lo) * unit(); }
-};
-
 constexpr int kWp = 16;
-constexpr int NL = PP_NUM_LANES;
-constexpr double kPi = 3.14159265358979323846;
-
-// lane tables of a ring of kWp waypoints, radius 120 m, driven counter-clockwise: lane r's centre
-// 4 (r + 0.5) m to the right of the waypoints (outside); and their arc prefix
-struct Ring {
-    std::vector<double> t, arc;
-    ppsynth::LaneTables T;
-    ppfollow::ArcTables A;
-    Ring() : t((size_t)5 * NL * kWp), arc(ppfollow::arc_doubles(kWp)) {
-        double* lx = t.data();
-        double* ly = lx + NL * kWp;
-        double* sl = ly + NL * kWp;
-        double* tx = sl + NL * kWp;
-        double* ty = tx + NL * kWp;
-        for (int l = 0; l < NL; l++)
-            for (int i = 0; i < kWp; i++) {
-                const double r = 120.0 + 4.0 * (l + 0.5), a = 2 * kPi * i / kWp;
-                lx[l * kWp + i] = r * cos(a);
-                ly[l * kWp + i] = r * sin(a);
-            }
-        for (int l = 0; l < NL; l++)
-            for (int i = 0; i < kWp; i++) {
-                const int p = i == 0 ? kWp - 1 : i - 1;
-                const double dx = lx[l * kWp + i] - lx[l * kWp + p], dy = ly[l * kWp + i] - ly[l * kWp + p];
-                const double len = sqrt(dx * dx + dy * dy);
-                sl[l * kWp + i] = len;
-                tx[l * kWp + i] = dx / len;
-                ty[l * kWp + i] = dy / len;
-            }
-        T.n = kWp; T.lc_x = lx; T.lc_y = ly; T.seg_len = sl; T.tan_x = tx; T.tan_y = ty;
-        ppfollow::build_arc(sl, kWp, arc.data());
-        A = ppfollow::arc_tables(arc.data(), kWp);
-    }
-    // the point t of the way along segment seg of lane l, lat metres to the right
-    void point(int l, int seg, double t, double lat, double* x, double* y) const {
-        double vx, vy;
-        ppsynth::traffic_car(T, l, seg, t, lat, 0.0, x, y, &vx, &vy);
-    }
-};
-
-struct Follow {                   // pp_follow over exactly sized vectors
-    std::vector<int32_t> started, ego_seg, leader;
-    std::vector<double> desired, next_speed, gap;
-    Follow(int64_t S, int n) : started(S), ego_seg(S), leader(S * n), desired(S * n), next_speed(S * n), gap(S * n) {}
-    pp_follow view() {
-        pp_follow f;
-        f.started = started.data(); f.ego_seg = ego_seg.data(); f.desired = desired.data();
-        f.next_speed = next_speed.data(); f.leader = leader.data(); f.gap = gap.data();
-        return f;
-    }
-};
 
 struct Change {                   // pp_lane_change over exactly sized vectors
     std::vector<int32_t> started, n_changes, last_car, last_dir, wait, changes, dir;
@@ -112,37 +35,11 @@ struct Change {                   // pp_lane_change over exactly sized vectors
     }
 };
 
-struct Traffic {
-    int64_t S;
-    int n;
-    std::vector<int32_t> lane, seg;
-    std::vector<double> t, off, v;
-    Traffic(int64_t S_, int n_) : S(S_), n(n_), lane(S_ * n_), seg(S_ * n_), t(S_ * n_), off(S_ * n_), v(S_ * n_) {}
-    ppsynth::TrafficV view() {
-        ppsynth::TrafficV tv;
-        tv.S = S; tv.n = n; tv.lane = lane.data(); tv.seg = seg.data(); tv.t = t.data(); tv.off = off.data(); tv.v = v.data();
-        return tv;
-    }
-};
-
-pp_follow_cfg follow_cfg() {      // include/pp.h pp_follow_cfg_default
-    pp_follow_cfg c;
-    memset(&c, 0, sizeof(c));
-    c.max_acc = 2.0; c.comfort_brake = 3.0; c.max_brake = 8.0; c.time_headway = 1.2; c.min_gap = 2.0;
-    c.gap_floor = 0.5; c.horizon = 150; c.car_length = c.ego_length = 4.5; c.lateral_reach = 2.0; c.react_to_ego = 1;
-    return c;
-}
-
-pp_lane_change_cfg change_cfg() {  // include/pp.h pp_lane_change_cfg_default
-    pp_lane_change_cfg c;
-    memset(&c, 0, sizeof(c));
-    c.politeness = 0.3; c.threshold = 0.2; c.right_bias = 0; c.safe_brake = 3.0; c.lateral_speed = 1.5;
-    c.ego_desired_speed = 22.2; c.min_interval_steps = 250;
-    return c;
-}
+pp_follow_cfg follow_cfg() { return default_of(ppfollow::cfg_default); }
+pp_lane_change_cfg change_cfg() { return default_of(pplanechange::cfg_default); }
 
 void frame(const Ring& R, const std::vector<double>& ex, const std::vector<double>& ey, const std::vector<double>& mph,
-           Traffic& tr, int consume, const pp_follow_cfg& fc, Follow& fo, const pp_lane_change_cfg& lc, Change& ch,
+           Traffic& tr, int consume, const pp_follow_cfg& fc, FollowState& fo, const pp_lane_change_cfg& lc, Change& ch,
            bool with_follow = true) {
     const pp_follow f = fo.view();
     const pp_lane_change l = ch.view();
@@ -151,11 +48,6 @@ void frame(const Ring& R, const std::vector<double>& ex, const std::vector<doubl
         if (with_follow) ppfollow::follow_scene(R.T, R.A, tr.S, s, ex[s], ey[s], mph[s], tv, consume, fc, f);
         pplanechange::lane_change_scene(R.T, R.A, tr.S, s, ex[s], ey[s], mph[s], tv, consume, fc, f, lc, l);
     }
-}
-
-void move(const Ring& R, Traffic& tr, int consume) {
-    for (size_t k = 0; k < tr.lane.size(); k++)
-        ppsynth::lane_advance(R.T, tr.lane[k], &tr.seg[k], &tr.t[k], tr.v[k] * 0.02 * consume);
 }
 
 void overtake(const Ring& R) {
@@ -171,7 +63,7 @@ void overtake(const Ring& R) {
         tr.off[0 * S + s] = 0.25; tr.off[1 * S + s] = -0.1;
         R.point(NL - 1, 9, 0.5, 3.0, &ex[s], &ey[s]);   // the ego across the ring, outside the outermost lane
     }
-    Follow fo(S, 2);
+    FollowState fo(S, 2);
     Change ch(S, 2);
     double x0, y0, x1, y1;
     R.point(1, 2, 2.0 / L, 0.25, &x0, &y0);
@@ -231,7 +123,7 @@ void random_frames(const Ring& R, uint64_t seed, int rounds) {
             tr.off[k] = g.uni(-1, 1); tr.v[k] = g.below(6) ? g.uni(0, 30) : 0.0;
             if (k >= (size_t)S && !g.below(10)) { tr.lane[k] = tr.lane[k - S]; tr.seg[k] = tr.seg[k - S]; tr.t[k] = tr.t[k - S]; }
         }
-        Follow fo(S, n_cars);
+        FollowState fo(S, n_cars);
         Change ch(S, n_cars);
         const int n_frames = 1 + g.below(40);
         std::vector<double> ex(S), ey(S), mph(S);
@@ -301,7 +193,7 @@ int main() {
     bad.min_interval_steps = -1;
     CHECK(!pplanechange::cfg_ok(bad));
     CHECK(pplanechange::cfg_ok(change_cfg()));
-    const Ring R;
+    const Ring R(kWp, 120.0);
     overtake(R);
     random_frames(R, 20261020, 300);
     if (g_fail) { fprintf(stderr, "%d checks failed\n", g_fail); return 1; }

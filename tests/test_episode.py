@@ -3,7 +3,7 @@ driven and judged — the previous path ahead of the ego, traffic placed at the 
 gaps, a warm judge state, a reset follow state.
 
 The definitions are the project's own (DESIGN.md "Episode starts"). Nothing restates the random
-stream: every claim is recomputed from the generator's outputs with NumPy, arcs from test_judge.Geo
+stream: every claim is recomputed from the generator's outputs with NumPy, arcs from world_lib.Geo
 (a cumulative sum over pp_map_geometry's polylines, not the library's walk), the required gap from the
 formula of DESIGN.md §15 written out below. Tolerances: positions within 1e-9 m (coordinates up to
 3e3 m carry 5e-13 m per operation; a walk adds at most 181 roundings of an arc up to 7e3 m, 2e-10 m);
@@ -14,18 +14,14 @@ Step numbers: a warm judge state starts at steps = PP_JUDGE_RING, so driven step
 first_step = PP_JUDGE_RING + k."""
 import ctypes as C
 import hashlib
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import oracle_lib
 from oracle_lib import ppamd
-from test_judge import DT, LIB4, Geo, same_bits
+from world_lib import DT, MPH, Geo, run_lanes4, same_bits, to_np
 
-MPH = 2.237
 RING = ppamd.JUDGE_RING
 SEED = 20261020
 # SHA-256 of pp_synth_traffic_host(seed 7, scenes 0..299): every scene and table array in name order,
@@ -483,28 +479,13 @@ def test_argument_errors(cpu):
 
 
 # ---- 8: the four-lane build -------------------------------------------------------------------------------------
-def run_lanes4(marker):
-    assert os.path.exists(LIB4), f"{LIB4} not built (run __graft_entry__.build())"
-    env = dict(os.environ, PPAMD_LIB=LIB4, PP_ORACLE_SO=os.path.join(oracle_lib.REPO, "oracle", "liboracle_l4.so"),
-               PP_REF_SO=os.path.join(oracle_lib.REPO, "oracle", "_ref", "libppref_l4.so"))
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(oracle_lib.REPO, "tests", "episode_lanes4_cases.py"),
-                        "-x", "-q", "-s", "-m", marker, "-p", "no:cacheprovider"],
-                       cwd=oracle_lib.REPO, env=env, capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:], r.stderr[-2000:])
-    assert r.returncode == 0, r.stdout[-3000:]
-
-
 def test_four_lane_build_host():
     """The 4-lane library's starts use all four lanes and keep their gaps (tests/episode_lanes4_cases.py,
     a child process: a process loads one PP_NUM_LANES)."""
-    run_lanes4("not gpu")
+    run_lanes4("episode_lanes4_cases.py", "not gpu")
 
 
 # ---- GPU --------------------------------------------------------------------------------------------------------
-def to_np(d):
-    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in d.items() if v is not None}
-
-
 def device_start(m, S, seed=SEED, first=0, cfg=None, dev=None):
     import torch
     cfg = cfg if cfg is not None else ppamd.default_episode_cfg()
@@ -566,4 +547,4 @@ class TestEpisodeGPU:
         assert (ppamd.follow_to_numpy(follow)["started"] == 1).all()
 
     def test_four_lane_build_device(self):
-        run_lanes4("gpu")
+        run_lanes4("episode_lanes4_cases.py", "gpu")

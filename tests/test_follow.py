@@ -12,102 +12,23 @@ expression.
 Tolerances. `leader` is exact. `gap`, `speed` and `desired` within TOL = 1e-8 (test_judge's): one
 frame is a few dozen roundings of magnitudes <= 1e4 m (arcs up to 7e3 m carry 1e-12 m; the gap
 ratio squared times max_acc times dt stays below 1e-9 even at the gap floor). In the random frames
-a car whose ORACLE decision lies within TIE = 1e-9 of a tie (two candidates' centre gaps, the
+a car whose ORACLE decision lies within world_lib.FOLLOW_TIE = 1e-9 of a tie (two candidates' centre gaps, the
 ego's distance against lateral_reach, the net gap against horizon) is excluded from the comparison
 of that car; the excluded share is printed, asserted <= 1 %, and zero in the hand-made frames."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import oracle_lib
 from oracle_lib import ppamd
-from test_judge import COL, DT, LIB4, TOL, Geo, base_segment, same_bits, up
-from test_rollout import many_car_traffic
-
-TIE = 1e-9
-MPH = 2.237
+from world_lib import (COL, DT, TOL, Geo, base_segment, copy_traffic, frame_of, many_car_traffic, move, random_frame,
+                       run_lanes4, same_bits, scenes_of, to_np, up)
+from world_lib import FollowOracle as Oracle
 
 
 def cfg_dict(cfg):
     return {k: getattr(cfg, k) for k, _ in ppamd.FollowCfg._fields_}
-
-
-# ---- the oracle -----------------------------------------------------------------------------------
-class Oracle:
-    """The issue's definitions over S scenes at once. Carries only the desired speeds."""
-
-    def __init__(self, geo, cfg):
-        self.g, self.c = geo, cfg_dict(cfg)
-        self.desired = None
-        self.excluded = self.cars = 0
-
-    def ego_on_lanes(self, p):
-        """Arc and distance of the nearest point of every lane's polyline to p [S, 2]: [NL, S] each."""
-        g = self.g
-        ap = p[None, :, None, :] - g.A[:, None]                                    # [NL, S, n, 2]
-        tt = np.clip((ap * g.D[:, None]).sum(-1) / (g.D ** 2).sum(-1)[:, None], 0.0, 1.0)
-        q = ap - g.D[:, None] * tt[..., None]
-        d = np.sqrt((q ** 2).sum(-1))                                              # [NL, S, n]
-        k = d.argmin(-1)                                                           # [NL, S]
-        l = np.arange(g.NL)[:, None]
-        s = np.arange(p.shape[0])[None]
-        return g.cum0[l, k] + tt[l, s, k] * g.L[l, k], d[l, s, k]
-
-    def frame(self, ex, ey, mph, tr, consume):
-        """Returns (leader, gap, speed', ambiguous) [J, S] from the pre-frame state."""
-        g, c = self.g, self.c
-        J, S = tr["n_cars"], len(ex)
-        lane, v = tr["lane"][:J], tr["speed"][:J].astype(float)
-        if self.desired is None:
-            self.desired = v.copy()
-        v0 = self.desired
-        arc = g.cum0[lane, tr["seg"][:J]] + tr["t"][:J] * g.L[lane, tr["seg"][:J]]  # [J, S]
-        loop = g.tot[lane]
-        arc_e, dist_e = self.ego_on_lanes(np.stack([ex, ey], -1))
-        s_ix = np.arange(S)[None]
-        occ = (dist_e <= c["lateral_reach"]) & bool(c["react_to_ego"])
-        near_reach = (np.abs(dist_e - c["lateral_reach"]) <= TIE) & bool(c["react_to_ego"])
-        # candidates: column 0 the ego, column m + 1 car m (the rank order)
-        gc = np.full((J, J + 1, S), np.inf)
-        ge = arc_e[lane, s_ix] - arc
-        ge = np.where(ge < 0, ge + loop, ge)
-        gc[:, 0] = np.where(occ[lane, s_ix], ge, np.inf)
-        d = arc[None, :, :] - arc[:, None, :]                                      # [j, m, S]
-        j_ix, m_ix = np.arange(J)[:, None, None], np.arange(J)[None, :, None]
-        d = np.where((d < 0) | ((d == 0) & (m_ix > j_ix)), d + loop[:, None, :], d)
-        gc[:, 1:] = np.where((lane[None] == lane[:, None]) & (m_ix != j_ix), d, np.inf)
-        col = gc.argmin(1)                                                         # first minimum: lowest rank
-        gmin = np.take_along_axis(gc, col[:, None], 1)[:, 0]
-        srt = np.sort(gc, axis=1)
-        second = np.where(np.isfinite(srt[:, 1]), srt[:, 1], 1e300) if J else srt[:, 0]
-        amb = np.isfinite(srt[:, 0]) & (second - np.where(np.isfinite(srt[:, 0]), srt[:, 0], 0.0) <= TIE)
-        amb |= near_reach[lane, s_ix]
-        lead = np.where(col == 0, J, col - 1)
-        llen = np.where(col == 0, c["ego_length"], c["car_length"])
-        gap = gmin - (c["car_length"] + llen) / 2
-        amb |= np.abs(gap - c["horizon"]) <= TIE
-        has = np.isfinite(gmin) & (gap <= c["horizon"])
-        lead = np.where(has, lead, -1)
-        gap = np.where(has, gap, np.inf)
-        vl = np.where(lead == J, (np.asarray(mph) / MPH)[None], np.take_along_axis(v, np.clip(lead, 0, max(J - 1, 0)), 0)) \
-            if J else v
-        with np.errstate(divide="ignore", invalid="ignore"):
-            r = np.where(v0 > 0, v / np.where(v0 > 0, v0, 1.0), 0.0)
-            free = 1 - r ** 4
-            sstar = c["min_gap"] + np.maximum(0.0, v * c["time_headway"] +
-                                              v * (v - vl) / (2 * np.sqrt(c["max_acc"] * c["comfort_brake"])))
-            q = sstar / np.maximum(gap, c["gap_floor"])
-            a = c["max_acc"] * np.where(has, free - q ** 2, free)
-        a = np.maximum(a, -c["max_brake"])
-        vn = np.minimum(np.maximum(v + a * (consume * DT), 0.0), v0)
-        vn = np.where(v0 > 0, vn, v)
-        self.excluded += int(amb.sum())
-        self.cars += J * S
-        return lead, gap, vn, amb
 
 
 def close(got, want, what, keep=None):
@@ -120,28 +41,6 @@ def close(got, want, what, keep=None):
 
 
 # ---- inputs ---------------------------------------------------------------------------------------
-def point_on(geo, lane, seg, along, lat=0.0):
-    """The point `along` metres from the start of (lane, seg) by arc, `lat` metres to the right."""
-    sg, t = geo.place(np.array([lane]), np.array([seg]), np.array([0.0]), np.array([float(along)]))
-    u = geo.U[lane, sg[0]]
-    return geo.A[lane, sg[0]] + geo.D[lane, sg[0]] * t[0] + lat * np.array([u[1], -u[0]])
-
-
-def frame_of(geo, S, ego, rows):
-    """A frame: ego (lane, seg, metres along, metres right of the centre, m/s), scene s 0.013 (s % 97) m
-    farther on; cars from rows (lane, seg, metres from the segment's start, offset, speed), the same
-    in every scene."""
-    lane, seg, along, lat, ve = ego
-    p = np.stack([point_on(geo, lane, seg, along + 0.013 * (s % 97), lat) for s in range(S)])
-    tr = ppamd.alloc_traffic(S, n=max(len(rows), 1))
-    for j, (cl, cs, s_along, off, v) in enumerate(rows):
-        sg, t = geo.place(np.array([cl]), np.array([cs]), np.array([0.0]), np.array([float(s_along)]))
-        tr["lane"][j], tr["seg"][j], tr["t"][j], tr["offset"][j], tr["speed"][j] = cl, sg[0], t[0], off, v
-    tr["n_cars"] = len(rows)
-    return {"ex": np.ascontiguousarray(p[:, 0]), "ey": np.ascontiguousarray(p[:, 1]),
-            "mph": np.full(S, ve * MPH), "traffic": tr}
-
-
 def hand_cases(geo, S):
     """name -> (frame, cfg overrides): the issue's hand-made frames on the longest segment of lane 1
     (cars placed by arc from its start, so a row may lie on a later segment)."""
@@ -174,38 +73,6 @@ def hand_cases(geo, S):
 HAND = ["lone", "platoon", "wrap", "same_arc", "parked", "ego_in_lane", "ego_between", "ego_out_of_reach",
         "ignore_ego", "horizon", "overlap", "closing"]
 HAND_CALLS = 3          # the positions stay, the speeds go on: calls 2 and 3 have v < v0 (the free-road term)
-
-
-def random_frame(geo, S, n_cars, seed):
-    """Cars within 300 m around a random point per scene (random lane, speed U(0, 25), one in eight
-    parked), the ego there too, up to 6 m beside a random lane's centre."""
-    rng = np.random.default_rng(seed)
-    tr = ppamd.alloc_traffic(S, n=max(n_cars, 1))
-    base = rng.integers(0, geo.n, S)
-    J = n_cars
-    lane = rng.integers(0, geo.NL, (J, S))
-    sg, t = geo.place(lane, np.broadcast_to(base, (J, S)).copy(), np.zeros((J, S)), rng.uniform(0, 300, (J, S)))
-    tr["lane"][:J], tr["seg"][:J], tr["t"][:J] = lane, sg, t
-    tr["offset"][:J] = rng.uniform(-0.3, 0.3, (J, S))
-    tr["speed"][:J] = np.where(rng.integers(0, 8, (J, S)) == 0, 0.0, rng.uniform(0, 25, (J, S)))
-    tr["n_cars"] = n_cars
-    el = rng.integers(0, geo.NL, S)
-    along, lat = rng.uniform(0, 300, S), rng.uniform(-6, 6, S)
-    p = np.stack([point_on(geo, el[s], base[s], along[s], lat[s]) for s in range(S)])
-    return {"ex": np.ascontiguousarray(p[:, 0]), "ey": np.ascontiguousarray(p[:, 1]),
-            "mph": rng.uniform(0, 50, S), "traffic": tr}
-
-
-def scenes_of(fr, dev=None):
-    S = len(fr["ex"])
-    sc = ppamd.alloc_scenes(S, 1)
-    sc["ego_x"], sc["ego_y"], sc["ego_speed_mph"] = fr["ex"], fr["ey"], np.ascontiguousarray(fr["mph"], np.float64)
-    return sc if dev is None else {k: up(v, dev) for k, v in sc.items()}
-
-
-def copy_traffic(tr, dev=None):
-    out = {k: (np.array(v, copy=True) if isinstance(v, np.ndarray) else v) for k, v in tr.items()}
-    return out if dev is None else {k: up(v, dev) for k, v in out.items()}
 
 
 def run_lib(m, fr, cfg, calls, consume=3, dev=None, follow=None):
@@ -346,12 +213,6 @@ def test_random_frames_vs_oracle(cpu, n_cars, consume):
 
 
 # ---- exact properties -------------------------------------------------------------------------------
-def move(geo, tr, consume):
-    J = tr["n_cars"]
-    sg, t = geo.place(tr["lane"][:J], tr["seg"][:J], tr["t"][:J], tr["speed"][:J] * DT * consume)
-    tr["seg"][:J], tr["t"][:J] = sg, t
-
-
 def test_free_traffic_keeps_its_speed_bit_for_bit(cpu):
     """Every gap above the horizon and the ego out of reach: ten frames leave the speeds' bits alone."""
     geo, S = cpu["geo"], 7
@@ -536,28 +397,13 @@ def test_argument_errors(cpu):
 
 
 # ---- the four-lane build ------------------------------------------------------------------------------
-def run_lanes4(marker):
-    assert os.path.exists(LIB4), f"{LIB4} not built (run __graft_entry__.build())"
-    env = dict(os.environ, PPAMD_LIB=LIB4, PP_ORACLE_SO=os.path.join(oracle_lib.REPO, "oracle", "liboracle_l4.so"),
-               PP_REF_SO=os.path.join(oracle_lib.REPO, "oracle", "_ref", "libppref_l4.so"))
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(oracle_lib.REPO, "tests", "follow_lanes4_cases.py"),
-                        "-x", "-q", "-s", "-m", marker, "-p", "no:cacheprovider"],
-                       cwd=oracle_lib.REPO, env=env, capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:], r.stderr[-2000:])
-    assert r.returncode == 0, r.stdout[-3000:]
-
-
 def test_four_lane_build_host():
     """The 4-lane library follows an ego and a car on lane 3 (tests/follow_lanes4_cases.py, a child
     process: a process loads one PP_NUM_LANES)."""
-    run_lanes4("not gpu")
+    run_lanes4("follow_lanes4_cases.py", "not gpu")
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------
-def to_np(d):
-    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in d.items()}
-
-
 @pytest.mark.gpu
 class TestFollowGPU:
     @pytest.fixture(scope="class")
@@ -686,4 +532,4 @@ class TestFollowGPU:
         assert (runs[1][4]["leader"] == -1).all() and (runs[1][4]["started"] == 1).all()
 
     def test_four_lane_build_device(self):
-        run_lanes4("gpu")
+        run_lanes4("follow_lanes4_cases.py", "gpu")

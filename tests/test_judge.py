@@ -19,63 +19,20 @@ most 1 % of the judged steps in every test, and zero in the hand-made cases.
 An episode's v_0 is 0 (include/pp.h), so a drive that starts at speed registers an ACC incident at
 step acc_window; the hand-made clean drives start from rest."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import oracle_lib
 from oracle_lib import ppamd
-from test_rollout import many_car_traffic
+from world_lib import DT, TOL, Geo, base_segment, many_car_traffic, run_lanes4, same_bits, up
 
-DT = 0.02
-TOL = 1e-8
 TIE = 1e-6
 KINDS = len(ppamd.INC_KINDS)
 COL, SPD, ACC, JRK, OFF = range(KINDS)
-LIB4 = os.path.join(oracle_lib.REPO, "carnd-path-planning-project_amd", "ppamd", "libppamd_l4.so")
-
 
 def cfg_dict(cfg):
     return {k: getattr(cfg, k) for k, _ in ppamd.JudgeCfg._fields_}
-
-
-# ---- geometry shared by the oracle and the case builders (from pp_map_geometry) -----------------
-class Geo:
-    def __init__(self, geom):
-        self.n = geom.shape[0]
-        self.NL = (geom.shape[1] - 4) // 2
-        self.B = np.stack([geom[:, 4 + 2 * l:6 + 2 * l] for l in range(self.NL)])   # segment i ends at lc[i]
-        self.A = np.roll(self.B, 1, axis=1)                                         # and starts at lc[i-1]
-        self.D = self.B - self.A
-        self.L = np.sqrt(self.D[..., 0] ** 2 + self.D[..., 1] ** 2)
-        self.U = self.D / self.L[..., None]
-        self.cum0 = np.cumsum(self.L, axis=1) - self.L                              # arc length at the segment's start
-        self.tot = self.L.sum(axis=1)
-
-    def place(self, lane, seg, t, dist):
-        """(seg, t) of a point `dist` metres on from (seg, t) along its lane polyline, by arc length."""
-        a = np.mod(self.cum0[lane, seg] + t * self.L[lane, seg] + dist, self.tot[lane])
-        seg2 = np.zeros_like(seg)
-        for l in range(self.NL):
-            m = lane == l
-            seg2[m] = np.searchsorted(self.cum0[l], a[m], side="right") - 1
-        return seg2, (a - self.cum0[lane, seg2]) / self.L[lane, seg2]
-
-    def car(self, lane, seg, t, off):
-        """Centre and unit tangent of a car: on the polyline, `off` along the right-hand normal."""
-        u = self.U[lane, seg]
-        p = self.A[lane, seg] + self.D[lane, seg] * t[..., None]
-        return p + np.stack([u[..., 1], -u[..., 0]], -1) * off[..., None], u
-
-    def lane_dist(self, p):
-        """Distance from p [S, 2] to the nearest lane-centre polyline: every segment of every lane."""
-        ap = p[:, None, None, :] - self.A[None]
-        tt = np.clip((ap * self.D[None]).sum(-1) / (self.D ** 2).sum(-1)[None], 0.0, 1.0)
-        q = ap - self.D[None] * tt[..., None]
-        return np.sqrt((q ** 2).sum(-1).reshape(len(p), -1).min(axis=1))
 
 
 def perp(a):
@@ -232,20 +189,7 @@ def compare(got, o, hand=False):
     return worst
 
 
-def same_bits(a, b, what=""):
-    for k in a:
-        x, y = np.ascontiguousarray(a[k]), np.ascontiguousarray(b[k])
-        assert x.shape == y.shape and x.tobytes() == y.tobytes(), f"{what} {k}"
-
-
 # ---- inputs -------------------------------------------------------------------------------------
-def base_segment(geo, lane):
-    """The longest segment of `lane`: (seg, point 5 m into it, its direction, its right-hand normal)."""
-    seg = int(np.argmax(geo.L[lane]))
-    u = geo.U[lane, seg]
-    return seg, geo.A[lane, seg] + 5.0 * u, u, np.array([u[1], -u[0]])
-
-
 def track(geo, S, speeds, lane=1, lat=0.0):
     """Straight drive along the base segment of `lane`, `lat` metres to its right: points [n + 1, S, 2]
     (P[0] the start) with step speeds `speeds`; scene s starts 0.013 (s % 97) m farther on."""
@@ -321,11 +265,6 @@ def wrap_frames(geo, S, consume, parked=False, steps=90):
 
 
 WRAP_CFG = {"off_lane_steps": 40}
-
-
-def up(x, dev):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x)).to(dev) if isinstance(x, np.ndarray) else x
 
 
 def run_lib(m, frames, cfg, dev=None, judge=None):
@@ -567,21 +506,10 @@ def test_argument_errors(cpu):
                                        None, 0, None, C.byref(ok), None) == -1
 
 
-def run_lanes4(marker):
-    assert os.path.exists(LIB4), f"{LIB4} not built (run __graft_entry__.build())"
-    env = dict(os.environ, PPAMD_LIB=LIB4, PP_ORACLE_SO=os.path.join(oracle_lib.REPO, "oracle", "liboracle_l4.so"),
-               PP_REF_SO=os.path.join(oracle_lib.REPO, "oracle", "_ref", "libppref_l4.so"))
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(oracle_lib.REPO, "tests", "judge_lanes4_cases.py"),
-                        "-x", "-q", "-s", "-m", marker, "-p", "no:cacheprovider"],
-                       cwd=oracle_lib.REPO, env=env, capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:], r.stderr[-2000:])
-    assert r.returncode == 0, r.stdout[-3000:]
-
-
 def test_four_lane_build_host():
     """The 4-lane library's host twin judges all four lanes (tests/judge_lanes4_cases.py, a child
     process: a process loads one PP_NUM_LANES)."""
-    run_lanes4("not gpu")
+    run_lanes4("judge_lanes4_cases.py", "not gpu")
 
 
 # ---- GPU ------------------------------------------------------------------------------------------
@@ -679,4 +607,4 @@ class TestJudgeGPU:
         assert ncol >= 1
 
     def test_four_lane_build_device(self):
-        run_lanes4("gpu")
+        run_lanes4("judge_lanes4_cases.py", "gpu")

@@ -20,19 +20,15 @@ tie rule decides them. The left-out share is printed, asserted <= 1 % on the ran
 the hand-made frames."""
 import ctypes as C
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import oracle_lib
-import test_follow as tf
+import world_lib as wl
 from oracle_lib import ppamd
-from test_judge import DT, LIB4, TOL, Geo, base_segment, same_bits, up
-from test_follow import MPH, frame_of, point_on
-from test_rollout import many_car_traffic
+from world_lib import (DT, MPH, TOL, Geo, base_segment, frame_of, many_car_traffic, run_lanes4, same_bits, to_np,
+                       up)
 
 TIE = 1e-9
 INF = float("inf")
@@ -81,7 +77,7 @@ def oracle_call(geo, fcfg, lcfg, sc, tr, fo, lc, consume):
     ex, ey, mph = sc["ego_x"], sc["ego_y"], sc["ego_speed_mph"]
     J, S = int(tr["n_cars"]), len(ex)
     pre_tr, pre_lc = tr, lc
-    tr = tf.copy_traffic(tr)
+    tr = wl.copy_traffic(tr)
     lc = {k: v.copy() for k, v in lc.items()}
     amb = np.zeros(S, bool)
     if J == 0:
@@ -102,7 +98,7 @@ def oracle_call(geo, fcfg, lcfg, sc, tr, fo, lc, consume):
     wait = np.maximum(lc["wait"][:J] - consume, 0)
     transit = off != home
     arc = geo.cum0[lane, seg] + t * geo.L[lane, seg]
-    arc_e, dist_e = tf.Oracle(geo, fcfg).ego_on_lanes(np.stack([ex, ey], -1))       # [NL, S]
+    arc_e, dist_e = wl.FollowOracle(geo, fcfg).ego_on_lanes(np.stack([ex, ey], -1))       # [NL, S]
     react = bool(F["react_to_ego"])
     occ = (dist_e <= F["lateral_reach"]) & react
     amb |= ((np.abs(dist_e - F["lateral_reach"]) <= TIE) & react).any(0)
@@ -259,7 +255,7 @@ class Tally:
 def world(sc, tr, dev=None):
     S, n = len(sc["ego_x"]), tr["lane"].shape[0]
     xp = "numpy" if dev is None else "torch"
-    w = {"sc": {k: np.array(v, copy=True) for k, v in sc.items()}, "tr": tf.copy_traffic(tr)}
+    w = {"sc": {k: np.array(v, copy=True) for k, v in sc.items()}, "tr": wl.copy_traffic(tr)}
     if dev is not None:
         w["sc"] = {k: up(v, dev) for k, v in w["sc"].items()}
         w["tr"] = {k: up(v, dev) for k, v in w["tr"].items()}
@@ -269,12 +265,7 @@ def world(sc, tr, dev=None):
 
 
 def frame_world(fr, dev=None):
-    return world(tf.scenes_of(fr), fr["traffic"], dev)
-
-
-def to_np(d):
-    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else (v.copy() if isinstance(v, np.ndarray) else v))
-            for k, v in d.items()}
+    return world(wl.scenes_of(fr), fr["traffic"], dev)
 
 
 def snap(w):
@@ -299,7 +290,7 @@ def follow_then_change(m, w, consume=3, fcfg=None, lcfg=None, geo=None, tally=No
 
 
 def move(geo, tr, consume):
-    tf.move(geo, tr, consume)
+    wl.move(geo, tr, consume)
 
 
 # ---- hand-made frames --------------------------------------------------------------------------------
@@ -529,14 +520,14 @@ def episode_start(m, S, n_cars, seed, **over):
 
 @pytest.mark.parametrize("consume", [1, 3, 7])
 def test_random_frames_vs_oracle(cpu, consume):
-    """0 to 100 cars: test_follow's random frames (cars within 300 m, one in eight parked, the ego
+    """0 to 100 cars: world_lib.random_frame's frames (cars within 300 m, one in eight parked, the ego
     among them), the 100-car rollout starts and episode starts; three frames each, moved in between,
     so the later calls see cars in transit and waiting."""
     geo, m = cpu["geo"], cpu["m"]
     tally = Tally()
     lcfg = ppamd.default_lane_change_cfg(min_interval_steps=10)
-    worlds = [frame_world(tf.random_frame(geo, 40, n, 3000 + 10 * n + consume)) for n in (0, 1, 2, 5, 12, 33)]
-    worlds.append(frame_world(tf.random_frame(geo, 12, 100, 3100 + consume)))
+    worlds = [frame_world(wl.random_frame(geo, 40, n, 3000 + 10 * n + consume)) for n in (0, 1, 2, 5, 12, 33)]
+    worlds.append(frame_world(wl.random_frame(geo, 12, 100, 3100 + consume)))
     worlds.append(world(*many_car_traffic(m, 12, 31 + consume)))
     worlds.append(world(*many_car_traffic(m, 12, 41 + consume, dense=True)))
     worlds.append(world(*episode_start(m, 64, 12, 500 + consume)))
@@ -554,7 +545,7 @@ def test_random_frames_vs_oracle(cpu, consume):
 
 def test_untouched_scenes_and_reused_state(cpu):
     geo, m = cpu["geo"], cpu["m"]
-    fr = tf.random_frame(geo, 16, 12, 91)
+    fr = wl.random_frame(geo, 16, 12, 91)
     w = frame_world(fr)
     ppamd.traffic_follow(m, w["sc"], w["tr"], w["fo"])
     w["fo"]["started"][::2] = 0                          # half of the scenes: not started by follow
@@ -572,7 +563,7 @@ def test_untouched_scenes_and_reused_state(cpu):
     t = Tally()
     t.check(w["tr"], w["lc"], want_tr, want_lc, amb, 12)
     # a used state with `started` zeroed behaves as a fresh one
-    used = frame_world(tf.random_frame(geo, 16, 12, 92))
+    used = frame_world(wl.random_frame(geo, 16, 12, 92))
     for _ in range(4):
         follow_then_change(m, used, 3)
         move(geo, used["tr"], 3)
@@ -603,7 +594,7 @@ def lane_neighbours(geo, F, sc, tr, j_s):
     out = []
     J = int(tr["n_cars"])
     arc = geo.cum0[tr["lane"][:J], tr["seg"][:J]] + tr["t"][:J] * geo.L[tr["lane"][:J], tr["seg"][:J]]
-    arc_e, dist_e = tf.Oracle(geo, ppamd.default_follow_cfg()).ego_on_lanes(np.stack([sc["ego_x"], sc["ego_y"]], -1))
+    arc_e, dist_e = wl.FollowOracle(geo, ppamd.default_follow_cfg()).ego_on_lanes(np.stack([sc["ego_x"], sc["ego_y"]], -1))
     for j, s in j_s:
         l = tr["lane"][j, s]
         loop = geo.tot[l]
@@ -686,7 +677,7 @@ def test_passing(cpu):
     fast car ends more than a car length ahead of the slow one; with threshold +inf it never is."""
     geo, m = cpu["geo"], cpu["m"]
     fcfg = ppamd.default_follow_cfg(react_to_ego=0)
-    o = tf.Oracle(geo, fcfg)
+    o = wl.FollowOracle(geo, fcfg)
 
     def lead_of_fast(tr):                                # arcs of both cars on lane 1's polyline
         p = geo.car(tr["lane"][:2], tr["seg"][:2], tr["t"][:2], tr["offset"][:2])[0]
@@ -713,7 +704,7 @@ def test_passing(cpu):
 def test_argument_errors(cpu):
     geo = cpu["geo"]
     fr = overtake(geo, S=2)
-    sc = ppamd.add_car_table(tf.scenes_of(fr))
+    sc = ppamd.add_car_table(wl.scenes_of(fr))
     tr = fr["traffic"]
     b, T = ppamd.scene_struct(sc), ppamd.traffic_struct(tr)
     follow, lc = ppamd.alloc_follow(2, 2), ppamd.alloc_lane_change(2, 2)
@@ -783,21 +774,10 @@ def test_argument_errors(cpu):
 
 
 # ---- the four-lane build ------------------------------------------------------------------------------
-def run_lanes4(marker):
-    assert os.path.exists(LIB4), f"{LIB4} not built (run __graft_entry__.build())"
-    env = dict(os.environ, PPAMD_LIB=LIB4, PP_ORACLE_SO=os.path.join(oracle_lib.REPO, "oracle", "liboracle_l4.so"),
-               PP_REF_SO=os.path.join(oracle_lib.REPO, "oracle", "_ref", "libppref_l4.so"))
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(oracle_lib.REPO, "tests", "lane_change_lanes4_cases.py"),
-                        "-x", "-q", "-s", "-m", marker, "-p", "no:cacheprovider"],
-                       cwd=oracle_lib.REPO, env=env, capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:], r.stderr[-2000:])
-    assert r.returncode == 0, r.stdout[-3000:]
-
-
 def test_four_lane_build_host():
     """In the 4-lane library a car on lane 2 changes to lane 3 (tests/lane_change_lanes4_cases.py, a
     child process: a process loads one PP_NUM_LANES)."""
-    run_lanes4("not gpu")
+    run_lanes4("lane_change_lanes4_cases.py", "not gpu")
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------
@@ -841,10 +821,10 @@ class TestLaneChangeGPU:
         geo, m, dev = env["geo"], env["m"], env["dev"]
         begun = 0
         for n_cars, consume in ((0, 3), (1, 1), (2, 3), (12, 3), (33, 7), (100, 3)):
-            fr = tf.random_frame(geo, S, n_cars, 7000 + n_cars + S)
-            begun += device_equals_host(m, geo, tf.scenes_of(fr), fr["traffic"], dev, f"random {n_cars}", consume)
+            fr = wl.random_frame(geo, S, n_cars, 7000 + n_cars + S)
+            begun += device_equals_host(m, geo, wl.scenes_of(fr), fr["traffic"], dev, f"random {n_cars}", consume)
         fr = overtake(geo, S=S)
-        begun += device_equals_host(m, geo, tf.scenes_of(fr), fr["traffic"], dev, "overtake")
+        begun += device_equals_host(m, geo, wl.scenes_of(fr), fr["traffic"], dev, "overtake")
         sc, tr = episode_start(m, S, 30, 800 + S, extra_gap=5.0)
         begun += device_equals_host(m, geo, sc, tr, dev, "episode")
         assert begun >= S
@@ -943,4 +923,4 @@ class TestLaneChangeGPU:
         assert hl["n_changes"].sum() >= S
 
     def test_four_lane_build_device(self):
-        run_lanes4("gpu")
+        run_lanes4("lane_change_lanes4_cases.py", "gpu")

@@ -10,6 +10,7 @@ import pytest
 
 import oracle_lib
 from oracle_lib import ppamd
+from world_lib import many_car_traffic
 
 TOL = 1e-6
 G = np.load(oracle_lib.GOLDEN + "/rollout_golden.npz")
@@ -68,29 +69,6 @@ def test_restatement_vs_reference_live(cpu, seed, consume, rng):
     lr = oracle_lib.ref_rollout(cpu["rlib"], cpu["wx"], cpu["wy"], *b, 300, consume, rng)
     for k in LOG_KEYS + ["plan_x", "plan_y"]:
         np.testing.assert_array_equal(lo[k], lr[k], err_msg=k)
-
-
-def many_car_traffic(m, S, seed, n=100, dense=False):
-    """A rollout start with n cars (beyond the simulator's 12 and the former 64-car limit): the
-    synthetic start state's 12 cars plus n - 12 more around the whole loop (every 20th waypoint
-    segment, lanes rotated, other speeds), so a frame reports up to n rows of which the far ones
-    fail lane matching and leave the table. dense: the extra cars within +-12 segments of the start
-    instead (cars drive through each other and the ego: collisions, MAXBRAKE). Every car is in the
-    persistent table's id space (slots = n)."""
-    sc, tr = ppamd.synth_traffic_host(m, S, seed=seed, car_stride=n, slots=n)
-    nwp = m.geometry().shape[0]
-    big = ppamd.alloc_traffic(S, n=n)
-    for k in ("lane", "seg", "t", "offset", "speed"):
-        big[k][:12] = tr[k][:12]
-    for j in range(12, n):
-        b, r = j % 12, j // 12
-        big["lane"][j] = (tr["lane"][b] + r) % ppamd.NUM_LANES
-        big["seg"][j] = (tr["seg"][b] + (3 * r - 12 if dense else 20 * r)) % nwp
-        big["t"][j] = tr["t"][b]
-        big["offset"][j] = tr["offset"][b]
-        big["speed"][j] = tr["speed"][b] * (0.9 + 0.02 * r)
-    big["n_cars"] = n
-    return sc, big
 
 
 @pytest.mark.skipif(oracle_lib.load_ref() is None, reason="oracle/_ref not built (no reference here)")

@@ -11,14 +11,14 @@ sys.path[:0] = [os.path.join(REPO, "carnd-path-planning-project_amd"), os.path.j
 import torch  # noqa: E402
 import oracle_lib  # noqa: E402
 from oracle_lib import ppamd  # noqa: E402
-import test_rollout  # noqa: E402
+import world_lib  # noqa: E402
 
 
 def main():
     S, F, seed = int(sys.argv[1]) if len(sys.argv) > 1 else 64, 300, 23
     wx, wy = oracle_lib.highway_map()
     m = ppamd.Map(wx, wy)
-    sc, tr = test_rollout.many_car_traffic(m, S, seed)
+    sc, tr = world_lib.many_car_traffic(m, S, seed)
     a, b = oracle_lib.copy_state(sc, tr), oracle_lib.copy_state(sc, tr)
     dev = torch.device("cuda", 0)
     d = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in sc.items()}
