@@ -217,7 +217,7 @@ int32_t pp_debug_set(int32_t key, int32_t value) {
         case PP_DBG_SPLIT: ok = value >= 0 && value <= 2; break;
         case PP_DBG_SORT_CARS: ok = value >= 0 && value <= 2; break;
         case PP_DBG_PERSIST: ok = value >= 0 && value <= 2; break;
-        default: break;       // (PP_DBG_LAST_PARTS and PP_DBG_LAST_PERSIST are read-only)
+        default: break;       // (PP_DBG_LAST_PARTS, PP_DBG_LAST_PERSIST and PP_DBG_LAST_PERSIST_SHAPE are read-only)
     }
     if (!ok) return PP_ERR_ARG;
     g_dbg[key].store(value, std::memory_order_relaxed);

@@ -501,15 +501,20 @@ __device__ __forceinline__ void cand_store_slot(const CandSm& L, int nslot, doub
 // is taken through an empty asm statement, so the compiler computes the per-thread set-up where
 // each group uses it, as in the one-group kernels, and does not carry it in registers across the
 // candidate loop (hoisted out of the caller's loop it spills there)
-template <bool kSlow, int kMode, int kEmitIn = 0, bool kPreA = false, bool kLoop = false>
+// kShape: the group's shape is BASELINE config 5's, as compile-time constants (kShapeNS speeds, no
+// draws, kShapeSPB scenes per group in 256 threads, teams of kShapeTS): only the integer index
+// arithmetic, the loop bounds and the LDS pointer arithmetic change; the caller passes SPB =
+// kShapeSPB and BPS = 1 and has checked P.n_speeds and the block size
+constexpr int kShapeNS = 5, kShapeSPB = 17, kShapeTS = 256 / (NL * kShapeSPB) > 8 ? 8 : 256 / (NL * kShapeSPB);
+template <bool kSlow, int kMode, int kEmitIn = 0, bool kPreA = false, bool kLoop = false, bool kShape = false>
 __device__ __forceinline__ void cand_group(const MapG& mg, const pp_scene_batch& in, const pp_params& P,
                                            const PrepV& pv, const pp_result& out, int SPB, int BPS,
                                            double* rec, uint64_t* adjm, int64_t g, double* sm,
                                            double* wslot = nullptr) {
     constexpr bool emit_in = kEmitIn == 1 && kMode == 1;
     constexpr bool win_inline = kEmitIn == 2 && kMode == 1;
-    const int NS = P.n_speeds, Cv = NL * NS, N = P.n_points;
-    const int D = P.n_draws > 1 ? P.n_draws : 1;
+    const int NS = kShape ? kShapeNS : P.n_speeds, Cv = NL * NS, N = P.n_points;
+    const int D = kShape ? 1 : P.n_draws > 1 ? P.n_draws : 1;
     const int C = D * Cv;                     // candidates per scene (all draws)
     const int nslot = NL * SPB;
     // the block's LDS: CandLds's layout (pp_k_spline.h: the host's sizes and the step kernels' geometry
@@ -574,7 +579,7 @@ __device__ __forceinline__ void cand_group(const MapG& mg, const pp_scene_batch&
     if (kLoop && !kSlow) __syncthreads();
     else if (!__syncthreads_or(mine) && kSlow) return;      // whole block leaves: no flagged scene
     if (!kPreA) {   // phase A: a team of TS threads per slot (team_a1..a5), block barriers between the steps
-        int TS = (int)blockDim.x / nslot;
+        int TS = kShape ? kShapeTS : (int)blockDim.x / nslot;
         if (TS > 8) TS = 8;
         const int j = tid / TS, r = tid - j * TS;
         const bool act = j < NL * nsc && ((sSlow[j / NL] != 0) == kSlow);
@@ -819,6 +824,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kCandWaves)
 // leaves before it touches LDS. The groups themselves are cand_group<false, kMode>'s, bit for bit;
 // flagged scenes are left to k_cand<true>, launched after this kernel as after k_cand<false>.
 struct Persist {};
+struct PersistShape {};       // the same with cand_group's kShape
 // its arguments, one struct at offset 0 of the kernel-argument segment: each group reads what it
 // needs from there through a pointer the compiler cannot follow across groups (scalar loads, as the
 // one-group kernels issue them), because arguments held in scalar registers across the candidate
@@ -830,6 +836,7 @@ struct PersistArgs {
 template <class kTag, int kMode>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kCandWaves))) void k_cand(PersistArgs a0) {
     static_assert(kMode == 1, "the persistent K2 is reference mode's");
+    constexpr bool kShape = std::is_same<kTag, PersistShape>::value;
     typedef const __attribute__((address_space(4))) PersistArgs* KArg;
     extern __shared__ __attribute__((aligned(16))) double sm[];
     int64_t g = blockIdx.x;
@@ -838,8 +845,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kCandWaves)
         KArg ka = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(ka));
         const PersistArgs& a = *(const PersistArgs*)ka;
-        cand_group<false, kMode, 0, false, true>(a.mg, a.in, a.P, a.pv, a.out, a.SPB, 1, a.rec, a.adjm, g, sm, nullptr);
-        uint32_t* sNext = (uint32_t*)(sm + CandLds{a.SPB}.doubles());
+        cand_group<false, kMode, 0, false, true, kShape>(a.mg, a.in, a.P, a.pv, a.out, kShape ? kShapeSPB : a.SPB, 1, a.rec, a.adjm, g, sm, nullptr);
+        uint32_t* sNext = (uint32_t*)(sm + CandLds{kShape ? kShapeSPB : a.SPB}.doubles());
         if (threadIdx.x == 0) *sNext = atomicAdd(a.next, 1u);
         __syncthreads();
         g = (int64_t)gridDim.x + *sNext;

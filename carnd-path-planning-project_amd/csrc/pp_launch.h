@@ -349,6 +349,7 @@ struct EvalArgs {
     SortedCars srt = {};      // rows 0: not in use
     uint32_t* next = nullptr; // the persistent kernels' claim counters (kPersistCtr words, zero before K1)
     unsigned persist = 0;     // the persistent k_cand's blocks (0: the call takes k_cand<false>)
+    bool persist_shape = false;   // ... in the instantiation with config 5's shape as constants (cand_group's kShape)
 };
 
 // the stream's workspace at the call's size, then every argument of the call's launches: A is
@@ -656,8 +657,13 @@ int32_t launch_plain(const EvalArgs& A, const EvalPlan& p, const EvalEvents& E) 
             // resident blocks that claim their groups (at most one block per group), then the
             // checked instantiation over the flagged groups as after k_cand<false>
             const PersistArgs pa = {A.mg, A.B, A.P, A.pv, A.R, cg.spb, A.rec, A.adjm, cg.groups, A.next};
-            hipLaunchKernelGGL((k_cand<Persist, 1>), dim3(std::min(A.persist, nb)), dim3(cg.threads),
-                               CandLds{cg.spb}.bytes_persist(), st, pa);
+            // (config 5's shape takes the instantiation that has it as compile-time constants)
+            if (A.persist_shape)
+                hipLaunchKernelGGL((k_cand<PersistShape, 1>), dim3(std::min(A.persist, nb)), dim3(cg.threads),
+                                   CandLds{cg.spb}.bytes_persist(), st, pa);
+            else
+                hipLaunchKernelGGL((k_cand<Persist, 1>), dim3(std::min(A.persist, nb)), dim3(cg.threads),
+                                   CandLds{cg.spb}.bytes_persist(), st, pa);
             hipLaunchKernelGGL((k_cand<true, 1>), dim3(nslow), dim3(cg.threads), A.cand_lds, st, A.mg, A.B, A.P, A.pv, A.R,
                                cg.spb, cg.bps, A.rec, A.adjm, A.gb.bits, cg.groups, A.gb.list, A.gb.count, (int64_t)0, A.wslot);
         }
@@ -729,6 +735,9 @@ int32_t eval_impl(pp_map* M, const pp_scene_batch* in, const pp_params* prm, pp_
 #endif
     A.persist = p.persist && !p.step_fused ? persist_blocks(DS, p.cg, device) : 0;
     g_dbg[PP_DBG_LAST_PERSIST].store((int)A.persist, std::memory_order_relaxed);
+    A.persist_shape = A.persist && NL * kShapeSPB <= 64 && prm->n_speeds == kShapeNS && prm->n_points == 50 &&
+                      p.cg.spb == kShapeSPB && p.cg.threads == 256;
+    g_dbg[PP_DBG_LAST_PERSIST_SHAPE].store(A.persist_shape ? 1 : 0, std::memory_order_relaxed);
     if (p.step_fused) return launch_step(A, p, E, fio);
     // (the parts' flagged-group counts and, behind them, the persistent kernels' claim counters)
     if (hipMemsetAsync(A.gb.count, 0, (kPartMax + kPersistCtr) * sizeof(uint32_t), A.st) != hipSuccess) return PP_ERR_HIP;

@@ -895,7 +895,7 @@ TIMING_ALL, TIMING_K2 = 1, 2
 
 # pp_debug_set keys and launch shapes (include/pp.h PP_DBG_*, PP_SHAPE_*)
 DBG_PREP_GROUP, DBG_PREP_WAVES, DBG_SHAPE, DBG_POISON, DBG_SPLIT, DBG_LAST_PARTS, DBG_SORT_CARS = 0, 1, 2, 3, 4, 5, 6
-DBG_PERSIST, DBG_LAST_PERSIST = 7, 8
+DBG_PERSIST, DBG_LAST_PERSIST, DBG_LAST_PERSIST_SHAPE = 7, 8, 9
 SPLIT_AUTO, SPLIT_ON, SPLIT_OFF = 0, 1, 2
 PERSIST_AUTO, PERSIST_ON, PERSIST_OFF = 0, 1, 2
 SHAPE_AUTO, SHAPE_SPLIT, SHAPE_CAND_SMALL, SHAPE_STEP = 0, 1, 2, 3

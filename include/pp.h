@@ -669,6 +669,10 @@ int32_t pp_ws_accept_key(const char* key, char* out, int32_t cap);
  *                      such batch, 2 off (0: batches of more than 1,572,864 scenes)
  *   PP_DBG_LAST_PERSIST read-only: the resident block count of the last pp_eval's persistent K2
  *                      (its grid is that, or one block per group if fewer), 0 when it ran none
+ *   PP_DBG_LAST_PERSIST_SHAPE read-only: 1 when that persistent K2 was the instantiation with
+ *                      BASELINE config 5's shape as compile-time constants (5 speeds, 3 lanes, 17
+ *                      scenes per group in 256 threads; taken at 50 points), 0 when it was the
+ *                      generic one or none ran
  * Returns PP_ERR_ARG for an unknown key or value. */
 #define PP_DBG_PREP_GROUP  0
 #define PP_DBG_PREP_WAVES  1
@@ -679,7 +683,8 @@ int32_t pp_ws_accept_key(const char* key, char* out, int32_t cap);
 #define PP_DBG_SORT_CARS   6
 #define PP_DBG_PERSIST     7
 #define PP_DBG_LAST_PERSIST 8
-#define PP_DBG_KEYS        9
+#define PP_DBG_LAST_PERSIST_SHAPE 9
+#define PP_DBG_KEYS        10
 #define PP_SHAPE_SPLIT      1
 #define PP_SHAPE_CAND_SMALL 2
 #define PP_SHAPE_STEP       3
