@@ -1,4 +1,5 @@
-// pp_api_rollout.h — host: closed-loop rollouts, the judge and reactive traffic (C ABI).
+// pp_api_rollout.h — host: closed-loop rollouts, the judge, reactive traffic, the judge summary and
+// parameter sweeps (C ABI).
 // Part of pp_eval.hip's translation unit.
 #pragma once
 
@@ -69,20 +70,27 @@ bool stages_ok(const Stages& st, const pp_scene_batch* tel, const pp_traffic* tr
     return !change || (follow && lane_change_ok(st.lc, st.ls));
 }
 
+// every argument check of rollout_loop (no HIP call)
+bool rollout_ok(const pp_map* M, const pp_scene_batch* tel, const pp_traffic* traffic, const pp_params* prm,
+                const pp_rollout_cfg* cfg, const pp_result* res, const pp_rollout_log* log, int32_t device,
+                const Stages& st) {
+    if (!M || !tel || !prm || !cfg || !res || device < 0 || device >= kMaxDev || !traffic_ok(traffic, tel) ||
+        !stages_ok(st, tel, traffic, res, cfg->consume))
+        return false;
+    if (cfg->n_frames < 0 || cfg->consume < 1 || !(cfg->sensor_range >= 0) || prm->n_draws > 1 ||
+        prm->emit_paths || !tel->tab_valid || !tel->tab_lane || !tel->tab_s || !tel->tab_d ||
+        !tel->tab_vs || !tel->tab_vd || !tel->tab_vx || !tel->tab_vy || tel->car_stride < traffic->n_cars ||
+        tel->tab_slots < traffic->n_cars)
+        return false;
+    return !(log && log->plan_x && !log->plan_y);
+}
+
 // pp_rollout's loop, a frame in this order: pp_eval, k_follow, k_lane_change (not without cars),
 // k_judge, k_sim, each of the three only where its stage is asked for
 int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
                      const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
                      void* hip_stream, const Stages& st) {
-    if (!M || !tel || !prm || !cfg || !res || device < 0 || device >= kMaxDev || !traffic_ok(traffic, tel) ||
-        !stages_ok(st, tel, traffic, res, cfg->consume))
-        return PP_ERR_ARG;
-    if (cfg->n_frames < 0 || cfg->consume < 1 || !(cfg->sensor_range >= 0) || prm->n_draws > 1 ||
-        prm->emit_paths || !tel->tab_valid || !tel->tab_lane || !tel->tab_s || !tel->tab_d ||
-        !tel->tab_vs || !tel->tab_vd || !tel->tab_vx || !tel->tab_vy || tel->car_stride < traffic->n_cars ||
-        tel->tab_slots < traffic->n_cars)
-        return PP_ERR_ARG;
-    if (log && log->plan_x && !log->plan_y) return PP_ERR_ARG;
+    if (!rollout_ok(M, tel, traffic, prm, cfg, res, log, device, st)) return PP_ERR_ARG;
     if (tel->n_scenes == 0 || cfg->n_frames == 0) return PP_OK;
     const WorldDev W(M, device, st.fs != nullptr);      // (the arc prefix: the follow stage's)
     if (W.rc) return W.rc;
@@ -102,6 +110,55 @@ int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const 
         if (rc != PP_OK) return rc;
     }
     return PP_OK;
+}
+
+// every argument check of pp_judge_summary and its host twin (no HIP call)
+bool summary_ok(const pp_judge* js, int64_t S, const pp_summary_cfg* c, const pp_judge_stats* o) {
+    return c && judge_state_ok(js) && ppsummary::stats_ok(o) && ppsummary::cfg_ok(*c, S);
+}
+
+// The summary's launch geometry (no HIP call): false where a grid would not fit.
+bool summary_args(int64_t S, const pp_summary_cfg& c, SumArgs& A) {
+    A.S = S; A.E = c.scenes_per_group; A.G = ppsummary::n_groups(S, A.E);
+    A.tpg = ppsummary::n_tiles(A.E < S ? A.E : S);
+    A.R = c.out_stride ? c.out_stride : A.G; A.out_first = c.out_first;
+    A.B = c.hist_bins; A.inv_w = c.hist_bins / c.hist_max;
+    A.direct = A.tpg == 1;
+    if (A.G > 0x7fffffff || A.tpg > 0x7fffffff || A.G * A.tpg > 0x7fffffff || (A.G * A.B + 255) / 256 > 0x7fffffff)
+        return false;
+    // tiles per chunk: as many as leave kSumBlocks blocks or more, at most kSumChunkMax (1,024 blocks of
+    // 8 tiles at 2,097,152 scenes: four resident blocks on each of 256 CUs); no figure depends on it
+    constexpr int64_t kSumBlocks = 512;
+    const int64_t k = A.G * A.tpg / kSumBlocks;
+    A.K = (int)(k < 1 ? 1 : (k > kSumChunkMax ? kSumChunkMax : k));
+    if (A.K > A.tpg) A.K = A.tpg > 0 ? (int)A.tpg : 1;    // (no scenes: no tiles)
+    A.cpg = (A.tpg + A.K - 1) / A.K;
+    return true;
+}
+
+// k_summary_clear, k_summary_tiles and, for groups of more than one tile, k_summary_groups over the
+// records of the stream's workspace (the chunks' parts, then T_t of the two sums per tile; grown under
+// M->mu, which is held through the launches as in pp_eval); arguments checked by the caller
+int launch_summary(pp_map* M, const pp_judge* js, const SumArgs& A, const pp_judge_stats* o, int32_t device,
+                   void* hip_stream) {
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int64_t blocks = A.G * A.cpg, tiles = A.G * A.tpg;
+    DeviceGuard g(device);
+    std::lock_guard<std::mutex> lk(M->mu);
+    SumRecs rec = {nullptr, nullptr, nullptr};
+    if (!A.direct) {
+        DevMem<>& W = M->dev[device].sws[hip_stream].sum;
+        const size_t bytes = sizeof(ppsummary::Part) * (size_t)blocks + 2 * sizeof(double) * (size_t)tiles;
+        const int rc = W.grow(st, (int64_t)bytes, bytes);
+        if (rc) return rc;
+        rec.part = (ppsummary::Part*)W.get();
+        rec.td = (double*)(rec.part + blocks);
+        rec.tc = rec.td + tiles;
+    }
+    hipLaunchKernelGGL(k_summary_clear, dim3((unsigned)((A.G * A.B + 255) / 256)), dim3(256), 0, st, A, o->hist);
+    hipLaunchKernelGGL(k_summary_tiles, dim3((unsigned)blocks), dim3(256), 0, st, *js, A, *o, rec);
+    if (!A.direct) hipLaunchKernelGGL(k_summary_groups, dim3((unsigned)A.G), dim3(256), 0, st, A, rec, *o);
+    return hipGetLastError() == hipSuccess ? PP_OK : PP_ERR_HIP;
 }
 
 // the optional states as the episode functions take them: by value, zeroed where absent
@@ -258,6 +315,68 @@ int32_t pp_synth_episode_host(const pp_map* M, uint64_t seed, int64_t first_scen
     for (int64_t s = 0; s < o.S; s++)
         ppepisode::episode_scene(W.T, seed, first_scene + s, s, *cfg, gap, o, tel->tab_valid, tel->tab_id,
                                  (int)tel->tab_slots, tv, js, jstate != nullptr, fs, fstate != nullptr);
+    return PP_OK;
+}
+
+int32_t pp_judge_summary(pp_map* M, const pp_judge* state, int64_t n_scenes, const pp_summary_cfg* cfg,
+                         pp_judge_stats* stats, int32_t device, void* hip_stream) {
+    SumArgs A;
+    if (!M || device < 0 || device >= kMaxDev || !summary_ok(state, n_scenes, cfg, stats) ||
+        !summary_args(n_scenes, *cfg, A))
+        return PP_ERR_ARG;
+    if (n_scenes == 0) return PP_OK;
+    return launch_summary(M, state, A, stats, device, hip_stream);
+}
+
+int32_t pp_judge_summary_host(const pp_judge* state, int64_t n_scenes, const pp_summary_cfg* cfg,
+                              pp_judge_stats* stats) {
+    if (!summary_ok(state, n_scenes, cfg, stats)) return PP_ERR_ARG;
+    ppsummary::summarize_host(*state, n_scenes, *cfg, *stats);
+    return PP_OK;
+}
+
+// Every set is checked against every call of its round before the first launch; the rounds are then
+// the public entry points themselves, so a set's rows are what those calls made by hand produce.
+int32_t pp_rollout_sweep(pp_map* M, const pp_params* sets, const pp_sweep_cfg* cfg, const pp_episode_cfg* ecfg,
+                         const pp_judge_cfg* jcfg, const pp_follow_cfg* fcfg, const pp_lane_change_cfg* lcfg,
+                         pp_scene_batch* tel, pp_traffic* traffic, pp_result* res, pp_judge* jstate,
+                         pp_follow* fstate, pp_lane_change* lstate, pp_judge_stats* stats, int32_t device,
+                         void* hip_stream) {
+    pp_follow_cfg gap;
+    if (!sets || !cfg || cfg->n_sets < 1 || !jstate || !fstate || device < 0 || device >= kMaxDev ||
+        !episode_ok(M, cfg->first_scene, ecfg, fcfg, tel, traffic, jstate, fstate, &gap))
+        return PP_ERR_ARG;
+    const int64_t S = tel->n_scenes;
+    pp_traffic placed = *traffic;                       // as pp_synth_episode leaves it
+    placed.n_cars = ecfg->n_cars;
+    const Stages st{kFollow, jcfg, jstate, fcfg, fstate, lcfg, lstate};
+    for (int p = 0; p < cfg->n_sets; p++)
+        if (!rollout_ok(M, tel, &placed, &sets[p], &cfg->rollout, res, nullptr, device, st) ||
+            eval_check(M, tel, &sets[p], res, device) != PP_OK)
+            return PP_ERR_ARG;
+    pp_summary_cfg sc = cfg->summary;
+    if (sc.scenes_per_group < 1) return PP_ERR_ARG;
+    const int64_t G = ppsummary::n_groups(S, sc.scenes_per_group);
+    sc.out_first = 0;
+    sc.out_stride = cfg->n_sets * G;
+    SumArgs A;
+    if (!summary_ok(jstate, S, &sc, stats) || !summary_args(S, sc, A)) return PP_ERR_ARG;
+    if (S == 0) return PP_OK;
+    for (int p = 0; p < cfg->n_sets; p++) {
+        int rc = pp_synth_episode(M, cfg->seed, cfg->first_scene, ecfg, fcfg, tel, traffic, jstate, fstate, device,
+                                  hip_stream);
+        if (rc == PP_OK && lstate) {
+            DeviceGuard g(device);
+            if (hipMemsetAsync(lstate->started, 0, sizeof(int32_t) * (size_t)S, (hipStream_t)hip_stream) != hipSuccess)
+                rc = PP_ERR_HIP;
+        }
+        if (rc == PP_OK)
+            rc = pp_rollout_lane_changing(M, tel, traffic, &sets[p], &cfg->rollout, res, nullptr, device, hip_stream,
+                                          jcfg, jstate, fcfg, fstate, lcfg, lstate);
+        sc.out_first = p * G;
+        if (rc == PP_OK) rc = pp_judge_summary(M, jstate, S, &sc, stats, device, hip_stream);
+        if (rc != PP_OK) return rc;
+    }
     return PP_OK;
 }
 

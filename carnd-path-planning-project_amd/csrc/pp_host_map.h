@@ -101,6 +101,7 @@ struct StreamWS {
     DevMem<> rec;                 // reference-mode winner record (capacity: scenes)
     DevMem<uint32_t> gbits;       // k_cand groups holding a kLimSlow scene (bitmap; all zero between calls; capacity: words)
     DevMem<> srt;                 // k_sort_cars' visit-major rows (SortedCars; capacity: bytes)
+    DevMem<> sum;                 // the judge summary's chunk parts and tile sums (SumRecs; capacity: bytes)
     Stream st2[kSplitMax - 1];    // the split's other streams (shard-sized batches)
     Event fork, join[kSplitMax - 1];
 };

@@ -1,5 +1,5 @@
 // pp_k_world.h — device: what surrounds the evaluator. The closed-loop rollout's simulator shim, judge
-// and car-following, lane-changing traffic (k_sim, k_judge, k_follow, k_lane_change), scene synthesis (k_synth*), the map tables'
+// and car-following, lane-changing traffic (k_sim, k_judge, k_follow, k_lane_change), the judge summary (k_summary_*), scene synthesis (k_synth*), the map tables'
 // kernels (Map::Init, src/main.cpp:89-131) and k_libm. Part of pp_eval.hip's translation unit.
 #pragma once
 
@@ -126,6 +126,191 @@ __global__ __launch_bounds__(256) void k_lane_change(ppsynth::LaneTables LT, ppf
     if (s >= S) return;
     pplanechange::lane_change_scene(LT, AT, S, s, ego_x[s], ego_y[s], ego_speed_mph[s], tr, consume, fcfg, fst, cfg,
                                     st);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Judge summary (include/pp.h pp_judge_summary; csrc/pp_summary.h): the world's one reduction across
+// lanes and blocks. k_summary_tiles: one block of 256 per chunk of K consecutive 256-scene tiles of a
+// group; in tile t lane i reads scene g E + 256 t + i of every array (contiguous), T_t is made per
+// tile, everything else is kept per lane over the chunk and reduced once (block_part).
+// k_summary_groups: one block per group, lane i the tiles t = i (mod 256) in ascending order and the
+// chunks' parts. The FP64 sums are the fixed expression of pp_summary.h (no FP64 atomic anywhere);
+// integers, minima and maxima are exact in any order, so no figure depends on K.
+// ------------------------------------------------------------------------------------------------
+struct SumArgs {
+    int64_t S, E, G;              // scenes, scenes per group, groups
+    int64_t tpg;                  // tiles of a full group
+    int64_t cpg;                  // chunks of a full group, ceil(tpg / K) (the grid: G cpg blocks)
+    int64_t R, out_first;         // rows the stats arrays hold, row of group 0
+    double inv_w;                 // hist_bins / hist_max
+    int B;                        // hist_bins
+    int K;                        // tiles per chunk, 1..kSumChunkMax
+    int direct;                   // tpg == 1: k_summary_tiles writes the rows itself, no records
+};
+constexpr int kSumChunkMax = 8;   // (block_part packs a wave's sums of the per-lane counts in 16 bits: 8 x 64 < 65,536)
+
+// the workspace behind the chunks' parts: T_t of dist and of clean_dist per tile
+struct SumRecs {
+    ppsummary::Part* part;        // [g cpg + c]
+    double* td;                   // [g tpg + t]
+    double* tc;
+};
+
+template <class T, class Op>
+__device__ __forceinline__ T wave_all(T v, Op op) {        // every lane gets the wave's result
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1) v = op(v, __shfl_xor(v, w));
+    return v;
+}
+
+// tree256 of the 256 values the block's lanes have stored in s_d and in s_c, after the barrier that
+// follows the stores, by wave 0 (valid in its lane 0): w = 128 and 64 as one read of four LDS entries
+// added in the tree's own order, w <= 32 as wave64 shuffles (lane i < w: v[i] += v[i + w]; what the
+// lanes beyond compute is never read).
+__device__ __forceinline__ void tree256_wave0(const double* s_d, const double* s_c, int lane, double& a, double& c) {
+    a = (s_d[lane] + s_d[lane + 128]) + (s_d[lane + 64] + s_d[lane + 192]);
+    c = (s_c[lane] + s_c[lane + 128]) + (s_c[lane + 64] + s_c[lane + 192]);
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1) {
+        a = a + __shfl_down(a, w);
+        c = c + __shfl_down(c, w);
+    }
+}
+
+// The block's part from its 256 lanes' parts, all but the two sums, valid in thread 0 after the call
+// (which holds one barrier): per wave by butterflies, the four waves' results combined through LDS.
+// kPacked: the eight per-lane counts are a chunk's (at most kSumChunkMax) and go two to a 32-bit word.
+template <bool kPacked>
+__device__ __forceinline__ void block_part(ppsummary::Part& p, ppsummary::Part* s_w) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const auto add = [](long long a, long long b) { return a + b; };
+    const auto uadd = [](uint32_t a, uint32_t b) { return a + b; };
+    const auto umin = [](uint32_t a, uint32_t b) { return b < a ? b : a; };
+    const auto dmin = [](double a, double b) { return b < a ? b : a; };
+    const auto dmax = [](double a, double b) { return b > a ? b : a; };
+    ppsummary::Part r;
+    r.dist_sum = 0.0; r.clean_sum = 0.0; r.bin = -1;
+    r.clean_min = wave_all(p.clean_min, dmin); r.clean_max = wave_all(p.clean_max, dmax);
+    r.min_sep = wave_all(p.min_sep, dmin);
+    r.max_mph = wave_all(p.max_mph, dmax); r.max_acc = wave_all(p.max_acc, dmax);
+    r.max_jerk = wave_all(p.max_jerk, dmax);
+    if (kPacked) {
+        const uint32_t w0 = wave_all((uint32_t)p.n_unjudged | ((uint32_t)p.n_nonfinite << 16), uadd);
+        const uint32_t w1 = wave_all((uint32_t)p.n_clean | ((uint32_t)p.with[0] << 16), uadd);
+        const uint32_t w2 = wave_all((uint32_t)p.with[1] | ((uint32_t)p.with[2] << 16), uadd);
+        const uint32_t w3 = wave_all((uint32_t)p.with[3] | ((uint32_t)p.with[4] << 16), uadd);
+        static_assert(PP_INC_KINDS == 5, "the packing above holds five kinds");
+        r.n_unjudged = w0 & 0xFFFF; r.n_nonfinite = w0 >> 16;
+        r.n_clean = w1 & 0xFFFF; r.with[0] = w1 >> 16;
+        r.with[1] = w2 & 0xFFFF; r.with[2] = w2 >> 16;
+        r.with[3] = w3 & 0xFFFF; r.with[4] = w3 >> 16;
+    } else {
+        r.n_unjudged = wave_all((long long)p.n_unjudged, add);
+        r.n_nonfinite = wave_all((long long)p.n_nonfinite, add);
+        r.n_clean = wave_all((long long)p.n_clean, add);
+#pragma unroll
+        for (int k = 0; k < PP_INC_KINDS; k++) r.with[k] = wave_all((long long)p.with[k], add);
+    }
+    r.steps = wave_all((long long)p.steps, add);
+#pragma unroll
+    for (int k = 0; k < PP_INC_KINDS; k++) {
+        r.steps_in[k] = wave_all((long long)p.steps_in[k], add);
+        r.first[k] = wave_all(p.first[k], umin);
+    }
+    if (lane == 0) s_w[wv] = r;
+    __syncthreads();
+    if (tid == 0) {
+        p = s_w[0];
+        ppsummary::merge(p, s_w[1]);
+        ppsummary::merge(p, s_w[2]);
+        ppsummary::merge(p, s_w[3]);
+    }
+}
+
+// rows out_first .. out_first + G - 1 of the histogram to zero (k_summary_tiles adds into them)
+__global__ __launch_bounds__(256) void k_summary_clear(SumArgs A, int64_t* hist) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.G * A.B) return;
+    const int64_t b = i / A.G, g = i - b * A.G;
+    hist[b * A.R + A.out_first + g] = 0;
+}
+
+// Chunk c of group g: tiles c K .. c K + K - 1 of the group, as far as it has scenes. Per tile: the
+// lanes' parts, T_t of the two sums to td / tc [g tpg + t]; the other figures stay in the lane's
+// running part and are reduced once per chunk into part [g cpg + c] (direct: into the row). The
+// histogram: B 32-bit LDS counters per block, the non-zero ones flushed once per chunk by one 64-bit
+// global integer add each. The sums' LDS arrays are double-buffered: a tile's stores go to the buffer
+// wave 0 is not reading, and the next barrier is behind those reads.
+__global__ __launch_bounds__(256) void k_summary_tiles(pp_judge st, SumArgs A, pp_judge_stats o, SumRecs rec) {
+    __shared__ double s_d[2][ppsummary::kTile], s_c[2][ppsummary::kTile];
+    __shared__ ppsummary::Part s_w[4];
+    __shared__ uint32_t s_h[PP_STATS_MAX_BINS];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t blk = blockIdx.x;
+    const int64_t g = blk / A.cpg, c = blk - g * A.cpg;
+    const int64_t s0 = g * A.E, n = A.S - s0 < A.E ? A.S - s0 : A.E;
+    const int64_t nt = ppsummary::n_tiles(n);
+    const int64_t t0 = c * A.K, t1 = t0 + A.K < nt ? t0 + A.K : nt;
+    for (int b = tid; b < A.B; b += 256) s_h[b] = 0;
+    __syncthreads();
+    ppsummary::Part acc;
+    ppsummary::part_none(acc);
+    double Td = 0.0, Tc = 0.0;
+    for (int64_t t = t0; t < t1; t++) {                    // (uniform over the block)
+        const int64_t k = t * ppsummary::kTile + tid;
+        const int buf = (int)(t - t0) & 1;
+        ppsummary::Part p;
+        if (k < n) ppsummary::scene_part(st, A.S, s0 + k, A.inv_w, A.B, p); else ppsummary::part_none(p);
+        if (p.bin >= 0) atomicAdd(&s_h[p.bin], 1u);
+        s_d[buf][tid] = p.dist_sum;
+        s_c[buf][tid] = p.clean_sum;
+        ppsummary::merge(acc, p);
+        __syncthreads();
+        if (wv == 0) {
+            tree256_wave0(s_d[buf], s_c[buf], lane, Td, Tc);
+            if (lane == 0 && !A.direct) { rec.td[g * A.tpg + t] = Td; rec.tc[g * A.tpg + t] = Tc; }
+        }
+    }
+    block_part<true>(acc, s_w);                            // (its barrier: the counters are complete)
+    const int64_t row = A.out_first + g;
+    for (int b = tid; b < A.B; b += 256) {
+        const uint32_t h = s_h[b];
+        if (h) atomicAdd((unsigned long long*)&o.hist[b * A.R + row], (unsigned long long)h);
+    }
+    if (tid != 0) return;
+    if (A.direct) {                                        // one tile: u_0 = +0.0 + T_0, tree256(u) = u_0
+        acc.dist_sum = 0.0 + Td;
+        acc.clean_sum = 0.0 + Tc;
+        ppsummary::write_row(o, A.R, row, n, acc);
+    } else {
+        rec.part[blk] = acc;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_summary_groups(SumArgs A, SumRecs rec, pp_judge_stats o) {
+    __shared__ double s_d[ppsummary::kTile], s_c[ppsummary::kTile];
+    __shared__ ppsummary::Part s_w[4];
+    const int tid = threadIdx.x;
+    const int64_t g = blockIdx.x;
+    const int64_t s0 = g * A.E, n = A.S - s0 < A.E ? A.S - s0 : A.E;
+    const int64_t nt = ppsummary::n_tiles(n), nc = (nt + A.K - 1) / A.K;
+    double ud = 0.0, uc = 0.0;
+    for (int64_t t = tid; t < nt; t += ppsummary::kTile) {             // u_i from +0.0, ascending t
+        ud = ud + rec.td[g * A.tpg + t];
+        uc = uc + rec.tc[g * A.tpg + t];
+    }
+    s_d[tid] = ud;
+    s_c[tid] = uc;
+    ppsummary::Part p;
+    ppsummary::part_none(p);
+    for (int64_t c = tid; c < nc; c += ppsummary::kTile) ppsummary::merge(p, rec.part[g * A.cpg + c]);
+    block_part<false>(p, s_w);                             // (its barrier: s_d and s_c are complete)
+    if (tid >= 64) return;
+    tree256_wave0(s_d, s_c, tid, ud, uc);
+    if (tid != 0) return;
+    p.dist_sum = ud;
+    p.clean_sum = uc;
+    ppsummary::write_row(o, A.R, A.out_first + g, n, p);
 }
 
 __global__ __launch_bounds__(256) void k_synth_traffic(ppsynth::LaneTables T, uint64_t seed, int64_t first,

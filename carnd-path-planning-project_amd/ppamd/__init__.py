@@ -166,6 +166,26 @@ class EpisodeCfg(C.Structure):
                 ("gap_slack", C.c_double)]
 
 
+class SummaryCfg(C.Structure):
+    _fields_ = [("scenes_per_group", C.c_int64), ("hist_bins", C.c_int32), ("_pad", C.c_int32),
+                ("hist_max", C.c_double), ("out_first", C.c_int64), ("out_stride", C.c_int64)]
+
+
+# the judge summary's rows (include/pp.h pp_judge_stats): name, dtype, leading dimension (None: [R],
+# a number k: [k, R], "b": [hist_bins, R])
+STATS_MAX_BINS = 1024
+STATS_FIELDS = [("n_scenes", "i8", None), ("n_unjudged", "i8", None), ("n_nonfinite", "i8", None),
+                ("n_clean", "i8", None), ("steps", "i8", None), ("scenes_with", "i8", len(INC_KINDS)),
+                ("steps_in", "i8", len(INC_KINDS)), ("first_step_min", "i4", len(INC_KINDS)),
+                ("dist_sum", "f8", None), ("clean_dist_sum", "f8", None), ("clean_dist_min", "f8", None),
+                ("clean_dist_max", "f8", None), ("min_sep", "f8", None), ("max_speed_mph", "f8", None),
+                ("max_acc", "f8", None), ("max_jerk", "f8", None), ("hist", "i8", "b")]
+
+
+class JudgeStats(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _, _ in STATS_FIELDS]
+
+
 class Params(C.Structure):
     _fields_ = [("n_points", C.c_int32), ("n_speeds", C.c_int32), ("cost_mode", C.c_int32),
                 ("emit_paths", C.c_int32), ("speed_offsets", C.c_double * MAX_SPEEDS),
@@ -175,6 +195,11 @@ class Params(C.Structure):
                 ("keep_distance_leeway", C.c_double), ("n_draws", C.c_int32), ("_pad_mc", C.c_int32),
                 ("noise_seed", C.c_uint64), ("noise_first_scene", C.c_int64),
                 ("noise_pos_sigma", C.c_double), ("noise_vel_sigma", C.c_double)]
+
+
+class SweepCfg(C.Structure):
+    _fields_ = [("n_sets", C.c_int32), ("_pad", C.c_int32), ("seed", C.c_uint64), ("first_scene", C.c_int64),
+                ("rollout", RolloutCfg), ("summary", SummaryCfg)]
 
 
 class SceneInfo(C.Structure):
@@ -213,7 +238,7 @@ EXPORTS = ["pp_params_default", "pp_num_candidates", "pp_version", "pp_map_creat
            "pp_follow_cfg_default", "pp_traffic_follow", "pp_traffic_follow_host", "pp_rollout_reactive",
            "pp_episode_cfg_default", "pp_synth_episode", "pp_synth_episode_host", "pp_math_eval",
            "pp_lane_change_cfg_default", "pp_traffic_lane_change", "pp_traffic_lane_change_host",
-           "pp_rollout_lane_changing"]
+           "pp_rollout_lane_changing", "pp_judge_summary", "pp_judge_summary_host", "pp_rollout_sweep"]
 
 
 def _load():
@@ -301,6 +326,17 @@ def _load():
                                              C.POINTER(Judge), C.POINTER(FollowCfg), C.POINTER(Follow),
                                              C.POINTER(LaneChangeCfg), C.POINTER(LaneChange)]
     lib.pp_rollout_lane_changing.restype = C.c_int32
+    lib.pp_judge_summary.argtypes = [C.c_void_p, C.POINTER(Judge), C.c_int64, C.POINTER(SummaryCfg),
+                                     C.POINTER(JudgeStats), C.c_int32, C.c_void_p]
+    lib.pp_judge_summary.restype = C.c_int32
+    lib.pp_judge_summary_host.argtypes = [C.POINTER(Judge), C.c_int64, C.POINTER(SummaryCfg), C.POINTER(JudgeStats)]
+    lib.pp_judge_summary_host.restype = C.c_int32
+    lib.pp_rollout_sweep.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(SweepCfg), C.POINTER(EpisodeCfg),
+                                     C.POINTER(JudgeCfg), C.POINTER(FollowCfg), C.POINTER(LaneChangeCfg),
+                                     C.POINTER(SceneBatch), C.POINTER(Traffic), C.POINTER(Result), C.POINTER(Judge),
+                                     C.POINTER(Follow), C.POINTER(LaneChange), C.POINTER(JudgeStats), C.c_int32,
+                                     C.c_void_p]
+    lib.pp_rollout_sweep.restype = C.c_int32
     lib.pp_synth_traffic.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.POINTER(SceneBatch),
                                      C.POINTER(Traffic), C.c_int32, C.c_void_p]
     lib.pp_synth_traffic.restype = C.c_int32
@@ -398,7 +434,7 @@ def _zeros(xp, device):
     if xp == "numpy":
         return lambda sh, dt: np.zeros(sh, dt)
     import torch
-    tdt = {"f8": torch.float64, "i4": torch.int32, "u4": torch.int32}
+    tdt = {"f8": torch.float64, "i4": torch.int32, "u4": torch.int32, "i8": torch.int64}
     return lambda sh, dt: torch.zeros(sh, dtype=tdt[dt], device=device)
 
 
@@ -786,6 +822,127 @@ def rollout_lane_changing(m, scenes, traffic, prm, result, follow, lane_change, 
     _rollout(lib.pp_rollout_lane_changing, "pp_rollout_lane_changing", m, scenes, traffic, prm, result, n_frames,
              consume, sensor_range, log, device, stream, *_judge_stage(judge, jcfg),
              fcfg if fcfg is not None else default_follow_cfg(), follow_struct(follow), *change)
+
+
+def alloc_judge_stats(rows, bins=64, xp="numpy", device=None):
+    """Zero arrays for `rows` rows of summary figures with a histogram of `bins` bins (pp_judge_stats)."""
+    mk = _zeros(xp, device)
+    return {k: mk((rows,) if lead is None else (bins if lead == "b" else lead, rows), dt)
+            for k, dt, lead in STATS_FIELDS}
+
+
+def stats_struct(st) -> JudgeStats:
+    return _struct(JudgeStats, [k for k, _, _ in STATS_FIELDS], st)
+
+
+def stats_to_numpy(st):
+    return _to_numpy(st)
+
+
+HIST_MAX_DEFAULT = 2000.0      # metres: above what 4,000 driven steps at the speed limit cover
+
+
+def judge_summary(judge, S, scenes_per_group=None, hist_bins=64, hist_max=HIST_MAX_DEFAULT, host=None, device=0,
+                  stream=None, m=None, stats=None, out_first=0):
+    """pp_judge_summary / pp_judge_summary_host: one row of figures per group of `scenes_per_group`
+    scenes (None: S, one row) of the judge state's first S scenes; returns the dict of arrays
+    (alloc_judge_stats). host=None picks the host twin when the arrays are numpy; the device call
+    needs the map `m`, whose stream workspace holds the tile partials. `stats`: write rows out_first..
+    of these arrays (they hold stats["n_scenes"].shape[0] rows) and leave the others alone."""
+    if host is None:
+        host = isinstance(judge["steps"], np.ndarray)
+    E = S if scenes_per_group is None else scenes_per_group
+    G = -(-S // E) if E >= 1 else 0
+    if stats is None:
+        if host:
+            stats = alloc_judge_stats(G, hist_bins)
+        else:
+            import torch
+            stats = alloc_judge_stats(G, hist_bins, xp="torch", device=torch.device("cuda", device))
+        stride = 0
+    else:
+        assert stats["hist"].shape[0] >= hist_bins, "stats hold fewer bins than hist_bins"
+        stride = int(stats["n_scenes"].shape[0])
+    cfg = SummaryCfg(E, hist_bins, 0, float(hist_max), out_first, stride)
+    J, O = judge_struct(judge), stats_struct(stats)
+    if host:
+        _check(lib.pp_judge_summary_host(_ref(J), S, _ref(cfg), _ref(O)), "pp_judge_summary_host")
+    else:
+        if m is None:
+            raise ValueError("judge_summary on the device needs the map m")
+        _check(lib.pp_judge_summary(m.handle, _ref(J), S, _ref(cfg), _ref(O), device, stream), "pp_judge_summary")
+    return stats
+
+
+def stats_quantile(stats, row, q, hist_max=HIST_MAX_DEFAULT):
+    """(lo, hi): the edges of the first histogram bin of `row` whose cumulative count reaches
+    ceil(q n), n the histogram's total; the clean_dist of rank ceil(q n) lies in [lo, hi) (the last
+    bin: hi = +inf, it also holds everything beyond hist_max). (nan, nan) for an empty histogram."""
+    import math
+    h = stats["hist"]
+    h = (h if isinstance(h, np.ndarray) else h.cpu().numpy())[:, row]
+    B, n = len(h), int(h.sum())
+    if n == 0:
+        return float("nan"), float("nan")
+    need = max(1, math.ceil(q * n))
+    b = int(np.searchsorted(np.cumsum(h), need))
+    inv_w = B / float(hist_max)
+
+    def edge(k):
+        # the kernel's bin is (int)(x * inv_w): bin k starts at the smallest x with x * inv_w >= k,
+        # which lies within a few ulps of k / inv_w (the product is monotone in x)
+        x = k / inv_w
+        while x * inv_w < k:
+            x = math.nextafter(x, math.inf)
+        while x > 0 and math.nextafter(x, -math.inf) * inv_w >= k:
+            x = math.nextafter(x, -math.inf)
+        return x
+
+    return edge(b), (math.inf if b == B - 1 else edge(b + 1))
+
+
+def rollout_sweep(m, sets, S, n_frames, scenes_per_group=None, seed=0x5EED0001, first=0, consume=3,
+                  sensor_range=300.0, hist_bins=64, hist_max=HIST_MAX_DEFAULT, ecfg=None, jcfg=None, fcfg=None,
+                  lcfg=None, lane_changes=True, device=0, stream=None, buffers=None):
+    """pp_rollout_sweep: drives the same S seeded episodes (synth_episode) once per parameter set of
+    `sets` (a list of Params) through rollout_lane_changing and summarises each drive per group of
+    `scenes_per_group` scenes (None: S), all on the one stream with no host synchronisation. Returns
+    (stats, buffers): the dict of device arrays of len(sets) * G rows, set p's group g in row p * G +
+    g, and the drive's buffers (scenes, traffic, result, judge, follow, lane_change: the last set's end
+    state), which a later call of the same sizes may pass back in."""
+    import torch
+    dev = torch.device("cuda", device)
+    ecfg = ecfg if ecfg is not None else default_episode_cfg()
+    jcfg = jcfg if jcfg is not None else default_judge_cfg()
+    fcfg = fcfg if fcfg is not None else default_follow_cfg()
+    E = S if scenes_per_group is None else scenes_per_group
+    G = -(-S // E) if E >= 1 else 0
+    P = len(sets)
+    n = max(int(ecfg.n_cars), 12)
+    if buffers is None:
+        big = default_params(n_speeds=max([int(p.n_speeds) for p in sets] + [1]),
+                             n_points=max([int(p.n_points) for p in sets] + [1]))
+        buffers = {"scenes": add_car_table(alloc_scenes(S, n, xp="torch", device=dev), slots=n, xp="torch", device=dev),
+                   "traffic": alloc_traffic(S, n=n, xp="torch", device=dev),
+                   "result": alloc_result(S, big, xp="torch", device=dev),
+                   "judge": alloc_judge(S, xp="torch", device=dev),
+                   "follow": alloc_follow(S, n=n, xp="torch", device=dev),
+                   "lane_change": alloc_lane_change(S, n=n, xp="torch", device=dev) if lane_changes else None}
+    lc = buffers.get("lane_change")
+    L = lane_change_struct(lc) if lc is not None else None
+    if lc is not None and lcfg is None:
+        lcfg = default_lane_change_cfg()
+    stats = alloc_judge_stats(P * G, hist_bins, xp="torch", device=dev)
+    arr = (Params * max(P, 1))(*sets)
+    cfg = SweepCfg(P, 0, seed, first, RolloutCfg(n_frames, consume, float(sensor_range)),
+                   SummaryCfg(E, hist_bins, 0, float(hist_max), 0, 0))
+    b, T, R = scene_struct(buffers["scenes"]), traffic_struct(buffers["traffic"]), result_struct(buffers["result"])
+    J, F, O = judge_struct(buffers["judge"]), follow_struct(buffers["follow"]), stats_struct(stats)
+    _check(lib.pp_rollout_sweep(m.handle, arr, _ref(cfg), _ref(ecfg), _ref(jcfg), _ref(fcfg),
+                                _ref(lcfg) if lc is not None else None, _ref(b), _ref(T), _ref(R), _ref(J), _ref(F),
+                                _ref(L), _ref(O), device, stream), "pp_rollout_sweep")
+    buffers["traffic"]["n_cars"] = int(ecfg.n_cars)
+    return stats, buffers
 
 
 def plan_reset(m, device=0):

@@ -570,6 +570,97 @@ int32_t pp_synth_episode_host(const pp_map* m, uint64_t seed, int64_t first_scen
                               const pp_follow_cfg* gap_rule, pp_scene_batch* telemetry, pp_traffic* traffic,
                               pp_judge* jstate, pp_follow* fstate);
 
+/* ---- judge summary: a judged batch as figures per group of scenes ------------------------------ */
+/* A judged drive ends as per-scene arrays (pp_judge). pp_judge_summary reduces them on the device to
+ * one row of figures per GROUP of scenes: groups are contiguous, scene s belongs to group
+ * g = s / scenes_per_group, G = ceil(S / scenes_per_group), the last group may be short (a sweep lays
+ * its sets out this way, shards concatenate this way, scenes_per_group = S gives one row). THIS
+ * LIBRARY'S OWN definitions (DESIGN.md "Judge summary and parameter sweeps" states them in full).
+ * A scene with steps[s] == 0 is UNJUDGED: a fresh state defines nothing else of it, so it counts in
+ * n_scenes and n_unjudged only. A judged scene whose dist or clean_dist is NaN or infinite counts in
+ * n_nonfinite and is left out of the four dist figures and the histogram, nothing else.
+ * The histogram of clean_dist: inv_w = hist_bins / hist_max (one host division), q = clean_dist inv_w,
+ * bin = q >= hist_bins - 1 ? hist_bins - 1 : (int)q (a negative clean_dist, which the judge never
+ * produces, counts in bin 0).
+ * The two sums are ONE FIXED EXPRESSION, the same bits on host and device and from run to run: with
+ * the group's values x_0.. in scene order (a scene left out counts +0.0), tile t = x[256 t .. 256 t +
+ * 255] padded with +0.0, tree256(v): for w = 128, 64, .., 1: v[i] += v[i + w] for i < w, result v[0];
+ * T_t = tree256(tile t); u_i = the sum from +0.0, in ascending t, of T_t over t = i (mod 256); the
+ * group's sum = tree256(u). Tiles start at the group's first scene: a row depends on its own group's
+ * scenes only. */
+#define PP_STATS_MAX_BINS 1024
+typedef struct pp_summary_cfg {
+    int64_t scenes_per_group;      /* E >= 1                                                        */
+    int32_t hist_bins;             /* B, 1..PP_STATS_MAX_BINS                                       */
+    int32_t _pad;
+    double  hist_max;              /* metres, finite, > 0: the clean_dist histogram covers [0, hist_max),
+                                      the last bin also holds everything beyond                     */
+    int64_t out_first;             /* row of group 0 in the stats arrays                            */
+    int64_t out_stride;            /* rows the stats arrays hold (0: G, and then out_first must be 0) */
+} pp_summary_cfg;
+
+/* Caller owned (device memory for pp_judge_summary and pp_rollout_sweep, host memory for
+ * pp_judge_summary_host); R = out_stride rows; per row [r], per kind [kind * R + r] (kind <
+ * PP_INC_KINDS), histogram [b * R + r] (b < hist_bins). */
+typedef struct pp_judge_stats {
+    int64_t* n_scenes;             /* scenes of the group                                          */
+    int64_t* n_unjudged;           /* steps[s] == 0; left out of everything below                  */
+    int64_t* n_nonfinite;          /* judged scenes whose dist or clean_dist is NaN or infinite    */
+    int64_t* n_clean;              /* judged scenes with flags == 0                                */
+    int64_t* steps;                /* sum of steps                                                 */
+    int64_t* scenes_with;          /* [kind * R + r] scenes with count[kind] > 0                   */
+    int64_t* steps_in;             /* [kind * R + r] sum of count[kind]                            */
+    int32_t* first_step_min;       /* [kind * R + r] smallest first_step > 0, 0: none              */
+    double*  dist_sum;             /* the two sums (the expression above)                          */
+    double*  clean_dist_sum;
+    double*  clean_dist_min;       /* +inf / -inf where the group has no finite judged scene       */
+    double*  clean_dist_max;
+    double*  min_sep;              /* min over judged scenes, NaN ignored (+inf stays +inf)        */
+    double*  max_speed_mph;        /* max over judged scenes, NaN ignored, -inf: none              */
+    double*  max_acc;
+    double*  max_jerk;
+    int64_t* hist;                 /* [b * R + r] scenes with a finite clean_dist in bin b         */
+} pp_judge_stats;
+
+/* Rows out_first .. out_first + G - 1 of `stats` are OVERWRITTEN, nothing else is written, `state` (S =
+ * n_scenes scenes) is only read. Device pointers; asynchronous on hip_stream, no host synchronisation
+ * (the tile partials live in the stream's workspace of `m`, which grows as pp_eval's does: calls on
+ * one stream are ordered by it, a call with more tiles than any before waits for the stream once).
+ * PP_ERR_ARG (before any HIP call) for a NULL map, state or stats array, scenes_per_group < 1,
+ * hist_bins outside 1..PP_STATS_MAX_BINS, hist_max not finite or not > 0, out_first < 0, out_stride
+ * neither 0 nor >= out_first + G, out_stride 0 with out_first != 0, n_scenes < 0 or a bad device;
+ * n_scenes == 0: PP_OK, nothing written. */
+int32_t pp_judge_summary(pp_map* m, const pp_judge* state, int64_t n_scenes, const pp_summary_cfg* cfg,
+                         pp_judge_stats* stats, int32_t device, void* hip_stream);
+/* The same on the host (host pointers; the same figures, bit for bit). */
+int32_t pp_judge_summary_host(const pp_judge* state, int64_t n_scenes, const pp_summary_cfg* cfg,
+                              pp_judge_stats* stats);
+
+/* ---- parameter sweeps: the same seeded episodes driven once per parameter set ------------------- */
+typedef struct pp_sweep_cfg {
+    int32_t  n_sets;               /* >= 1                                                          */
+    int32_t  _pad;
+    uint64_t seed;                 /* pp_synth_episode's seed and first scene: every set's starts   */
+    int64_t  first_scene;
+    pp_rollout_cfg rollout;
+    pp_summary_cfg summary;        /* out_first / out_stride are set by the sweep (ignored here):
+                                      set p's group g is row p * G + g of n_sets * G rows          */
+} pp_sweep_cfg;
+/* Per set p, in order, on the one stream and with no host synchronisation: pp_synth_episode(seed,
+ * first_scene, ecfg, fcfg as the gap rule, telemetry, traffic, jstate, fstate); lstate->started
+ * zeroed (where there is an lstate); pp_rollout_lane_changing of rollout.n_frames frames with
+ * sets[p] (no log); pp_judge_summary into rows p * G ... Set p's rows are, bit for bit, what those
+ * calls made by hand produce. `sets` is host memory; every other buffer is the caller's device state,
+ * sized for telemetry->n_scenes scenes, and `result` for the largest n_points and candidate count
+ * among the sets: THE CALLER'S DUTY. lcfg and lstate both NULL: no lane changes. PP_ERR_ARG before
+ * anything is launched for n_sets < 1, a NULL argument, or any set, configuration or state one of
+ * those calls would refuse. */
+int32_t pp_rollout_sweep(pp_map* m, const pp_params* sets, const pp_sweep_cfg* cfg,
+                         const pp_episode_cfg* ecfg, const pp_judge_cfg* jcfg, const pp_follow_cfg* fcfg,
+                         const pp_lane_change_cfg* lcfg, pp_scene_batch* telemetry, pp_traffic* traffic,
+                         pp_result* result, pp_judge* jstate, pp_follow* fstate, pp_lane_change* lstate,
+                         pp_judge_stats* stats, int32_t device, void* hip_stream);
+
 /* A batch in HOST memory (the batched onMessage; what a server calls per tick): stages the
  * scenes — and their car table when tab_valid is set, updated in place — through device memory,
  * runs pp_eval on hip_stream and copies winner, n_out, next_x/next_y, cost and status back into
