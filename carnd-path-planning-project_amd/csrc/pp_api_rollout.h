@@ -1,5 +1,5 @@
-// pp_api_rollout.h — host: closed-loop rollouts, the judge, reactive traffic, the judge summary and
-// parameter sweeps (C ABI).
+// pp_api_rollout.h — host: closed-loop rollouts, the judge, reactive traffic, the sensor model, the
+// judge summary and parameter sweeps (C ABI).
 // Part of pp_eval.hip's translation unit.
 #pragma once
 
@@ -22,6 +22,10 @@ int launch_lane_change(const WorldTables& W, const pp_scene_batch* tel, const pp
                        const pp_lane_change* ls, void* stream) {
     return launch_scenes(k_lane_change, tel->n_scenes, stream, W.T, W.AT, tel->n_scenes, tel->ego_x, tel->ego_y,
                          tel->ego_speed_mph, tv, consume, *fc, *fs, *lc, *ls);
+}
+
+int launch_sense(const pp_scene_batch* tel, const pp_sensor_cfg* sc, const pp_sensor* ss, void* stream) {
+    return launch_scenes(k_sense, tel->n_scenes, stream, truth_view(tel), *sc, *ss);
 }
 
 // every argument check of pp_synth_episode and its host twin (no HIP call); *gap: the gap rule in force
@@ -57,16 +61,19 @@ struct Stages {
     const pp_follow* fs = nullptr;
     const pp_lane_change_cfg* lc = nullptr;
     const pp_lane_change* ls = nullptr;
+    const pp_sensor_cfg* sc = nullptr;
+    const pp_sensor* ss = nullptr;
 };
 
 // each stage asked for against its own arguments and what it reads of a frame; lane changes read the
 // follow update's records, so they need that stage
 bool stages_ok(const Stages& st, const pp_scene_batch* tel, const pp_traffic* traffic, const pp_result* res,
                int32_t consume) {
-    const bool judge = st.jc || st.js, follow = st.fc || st.fs, change = st.lc || st.ls;
+    const bool judge = st.jc || st.js, follow = st.fc || st.fs, change = st.lc || st.ls, sense = st.sc || st.ss;
     if (((st.need & kJudge) && !judge) || ((st.need & kFollow) && !follow)) return false;
     if (judge && (!judge_ok(st.jc, st.js) || !judge_frame_ok(tel, traffic, res, consume))) return false;
     if (follow && (!follow_ok(st.fc, st.fs) || !follow_frame_ok(tel, traffic, consume))) return false;
+    if (sense && (!sense_frame_ok(tel) || !sensor_ok(st.sc, st.ss, tel->car_stride))) return false;
     return !change || (follow && lane_change_ok(st.lc, st.ls));
 }
 
@@ -85,8 +92,10 @@ bool rollout_ok(const pp_map* M, const pp_scene_batch* tel, const pp_traffic* tr
     return !(log && log->plan_x && !log->plan_y);
 }
 
-// pp_rollout's loop, a frame in this order: pp_eval, k_follow, k_lane_change (not without cars),
-// k_judge, k_sim, each of the three only where its stage is asked for
+// pp_rollout's loop, a frame in this order: k_sense, pp_eval, k_follow, k_lane_change (not without
+// cars), k_judge, k_sim, each of the four only where its stage is asked for. With the sensor pp_eval
+// plans from `seen`: the telemetry with the sensor state's rows in place of the truth's (the car table
+// is shared, so it is updated as before); every other stage reads and writes the truth.
 int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
                      const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
                      void* hip_stream, const Stages& st) {
@@ -99,8 +108,15 @@ int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const 
     A.range2 = cfg->sensor_range * cfg->sensor_range;
     if (log) A.log = *log; else memset(&A.log, 0, sizeof(A.log));
     const ppsynth::TrafficV tv = traffic_view(traffic, tel->n_scenes);
+    pp_scene_batch seen = *tel;
+    if (st.ss) {
+        seen.n_cars = st.ss->n_cars; seen.car_id = st.ss->car_id;
+        seen.car_x = st.ss->car_x; seen.car_y = st.ss->car_y;
+        seen.car_vx = st.ss->car_vx; seen.car_vy = st.ss->car_vy;
+    }
     for (int f = 0; f < cfg->n_frames; f++) {
-        int rc = pp_eval(M, tel, prm, res, device, hip_stream);
+        int rc = st.ss ? launch_sense(tel, st.sc, st.ss, hip_stream) : PP_OK;
+        if (rc == PP_OK) rc = pp_eval(M, &seen, prm, res, device, hip_stream);
         if (rc == PP_OK && st.fs) rc = launch_follow(W, tel, tv, cfg->consume, st.fc, st.fs, hip_stream);
         if (rc == PP_OK && st.ls && tv.n > 0)
             rc = launch_lane_change(W, tel, tv, cfg->consume, st.fc, st.fs, st.lc, st.ls, hip_stream);
@@ -283,6 +299,46 @@ int32_t pp_rollout_lane_changing(pp_map* M, pp_scene_batch* tel, pp_traffic* tra
                         Stages{kFollow, jstate ? jcfg : nullptr, jstate, fcfg, fstate, lcfg, lstate});
 }
 
+void pp_sensor_cfg_default(pp_sensor_cfg* c) { if (c) ppsensor::cfg_default(c); }
+
+double pp_sensor_gauss(uint64_t seed, int64_t scene, int32_t frame, int32_t car, int32_t q) {
+    uint32_t w[4];
+    ppsensor::block(seed, (uint64_t)scene, (uint32_t)frame, (uint32_t)car, q, w);
+    return ppsynth::ih_unit(w);
+}
+
+uint32_t pp_sensor_word(uint64_t seed, int64_t scene, int32_t frame, int32_t car) {
+    uint32_t w[4];
+    ppsensor::block(seed, (uint64_t)scene, (uint32_t)frame, (uint32_t)car, ppsensor::kDropBlock, w);
+    return w[0];
+}
+
+int32_t pp_sense_frame(const pp_scene_batch* tel, const pp_sensor_cfg* cfg, pp_sensor* state, int32_t device,
+                       void* hip_stream) {
+    if (device < 0 || device >= kMaxDev || !sense_frame_ok(tel) || !sensor_ok(cfg, state, tel->car_stride))
+        return PP_ERR_ARG;
+    if (tel->n_scenes == 0) return PP_OK;
+    DeviceGuard g(device);
+    return launch_sense(tel, cfg, state, hip_stream);
+}
+
+int32_t pp_sense_frame_host(const pp_scene_batch* tel, const pp_sensor_cfg* cfg, pp_sensor* state) {
+    if (!sense_frame_ok(tel) || !sensor_ok(cfg, state, tel->car_stride)) return PP_ERR_ARG;
+    const ppsensor::Truth T = truth_view(tel);
+    for (int64_t s = 0; s < T.S; s++) ppsensor::sense_scene(T, s, *cfg, *state);
+    return PP_OK;
+}
+
+// (a lone scfg or a lone sstate asks for the sensor and is refused; neither: none)
+int32_t pp_rollout_sensed(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
+                          const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
+                          void* hip_stream, const pp_judge_cfg* jcfg, pp_judge* jstate, const pp_follow_cfg* fcfg,
+                          pp_follow* fstate, const pp_lane_change_cfg* lcfg, pp_lane_change* lstate,
+                          const pp_sensor_cfg* scfg, pp_sensor* sstate) {
+    return rollout_loop(M, tel, traffic, prm, cfg, res, log, device, hip_stream,
+                        Stages{kFollow, jstate ? jcfg : nullptr, jstate, fcfg, fstate, lcfg, lstate, scfg, sstate});
+}
+
 void pp_episode_cfg_default(pp_episode_cfg* c) { if (c) ppepisode::cfg_default(c); }
 
 int32_t pp_synth_episode(pp_map* M, uint64_t seed, int64_t first_scene, const pp_episode_cfg* cfg,
@@ -335,13 +391,17 @@ int32_t pp_judge_summary_host(const pp_judge* state, int64_t n_scenes, const pp_
     return PP_OK;
 }
 
+}  // extern "C"
+
+namespace {
 // Every set is checked against every call of its round before the first launch; the rounds are then
 // the public entry points themselves, so a set's rows are what those calls made by hand produce.
-int32_t pp_rollout_sweep(pp_map* M, const pp_params* sets, const pp_sweep_cfg* cfg, const pp_episode_cfg* ecfg,
-                         const pp_judge_cfg* jcfg, const pp_follow_cfg* fcfg, const pp_lane_change_cfg* lcfg,
-                         pp_scene_batch* tel, pp_traffic* traffic, pp_result* res, pp_judge* jstate,
-                         pp_follow* fstate, pp_lane_change* lstate, pp_judge_stats* stats, int32_t device,
-                         void* hip_stream) {
+// sensors: a sensor per set and its state (pp_rollout_sweep_sensed), or both null (pp_rollout_sweep).
+int32_t sweep_impl(pp_map* M, const pp_params* sets, const pp_sweep_cfg* cfg, const pp_episode_cfg* ecfg,
+                   const pp_judge_cfg* jcfg, const pp_follow_cfg* fcfg, const pp_lane_change_cfg* lcfg,
+                   pp_scene_batch* tel, pp_traffic* traffic, pp_result* res, pp_judge* jstate,
+                   pp_follow* fstate, pp_lane_change* lstate, pp_judge_stats* stats, int32_t device,
+                   void* hip_stream, const pp_sensor_cfg* sensors, pp_sensor* sstate) {
     pp_follow_cfg gap;
     if (!sets || !cfg || cfg->n_sets < 1 || !jstate || !fstate || device < 0 || device >= kMaxDev ||
         !episode_ok(M, cfg->first_scene, ecfg, fcfg, tel, traffic, jstate, fstate, &gap))
@@ -349,11 +409,12 @@ int32_t pp_rollout_sweep(pp_map* M, const pp_params* sets, const pp_sweep_cfg* c
     const int64_t S = tel->n_scenes;
     pp_traffic placed = *traffic;                       // as pp_synth_episode leaves it
     placed.n_cars = ecfg->n_cars;
-    const Stages st{kFollow, jcfg, jstate, fcfg, fstate, lcfg, lstate};
-    for (int p = 0; p < cfg->n_sets; p++)
+    for (int p = 0; p < cfg->n_sets; p++) {
+        const Stages st{kFollow, jcfg, jstate, fcfg, fstate, lcfg, lstate, sensors ? &sensors[p] : nullptr, sstate};
         if (!rollout_ok(M, tel, &placed, &sets[p], &cfg->rollout, res, nullptr, device, st) ||
             eval_check(M, tel, &sets[p], res, device) != PP_OK)
             return PP_ERR_ARG;
+    }
     pp_summary_cfg sc = cfg->summary;
     if (sc.scenes_per_group < 1) return PP_ERR_ARG;
     const int64_t G = ppsummary::n_groups(S, sc.scenes_per_group);
@@ -370,14 +431,41 @@ int32_t pp_rollout_sweep(pp_map* M, const pp_params* sets, const pp_sweep_cfg* c
             if (hipMemsetAsync(lstate->started, 0, sizeof(int32_t) * (size_t)S, (hipStream_t)hip_stream) != hipSuccess)
                 rc = PP_ERR_HIP;
         }
+        if (rc == PP_OK && sstate) {
+            DeviceGuard g(device);
+            if (hipMemsetAsync(sstate->frame, 0, sizeof(int32_t) * (size_t)S, (hipStream_t)hip_stream) != hipSuccess)
+                rc = PP_ERR_HIP;
+        }
         if (rc == PP_OK)
-            rc = pp_rollout_lane_changing(M, tel, traffic, &sets[p], &cfg->rollout, res, nullptr, device, hip_stream,
-                                          jcfg, jstate, fcfg, fstate, lcfg, lstate);
+            rc = pp_rollout_sensed(M, tel, traffic, &sets[p], &cfg->rollout, res, nullptr, device, hip_stream, jcfg,
+                                   jstate, fcfg, fstate, lcfg, lstate, sensors ? &sensors[p] : nullptr, sstate);
         sc.out_first = p * G;
         if (rc == PP_OK) rc = pp_judge_summary(M, jstate, S, &sc, stats, device, hip_stream);
         if (rc != PP_OK) return rc;
     }
     return PP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t pp_rollout_sweep(pp_map* M, const pp_params* sets, const pp_sweep_cfg* cfg, const pp_episode_cfg* ecfg,
+                         const pp_judge_cfg* jcfg, const pp_follow_cfg* fcfg, const pp_lane_change_cfg* lcfg,
+                         pp_scene_batch* tel, pp_traffic* traffic, pp_result* res, pp_judge* jstate,
+                         pp_follow* fstate, pp_lane_change* lstate, pp_judge_stats* stats, int32_t device,
+                         void* hip_stream) {
+    return sweep_impl(M, sets, cfg, ecfg, jcfg, fcfg, lcfg, tel, traffic, res, jstate, fstate, lstate, stats, device,
+                      hip_stream, nullptr, nullptr);
+}
+
+int32_t pp_rollout_sweep_sensed(pp_map* M, const pp_params* sets, const pp_sweep_cfg* cfg, const pp_episode_cfg* ecfg,
+                                const pp_judge_cfg* jcfg, const pp_follow_cfg* fcfg, const pp_lane_change_cfg* lcfg,
+                                pp_scene_batch* tel, pp_traffic* traffic, pp_result* res, pp_judge* jstate,
+                                pp_follow* fstate, pp_lane_change* lstate, pp_judge_stats* stats, int32_t device,
+                                void* hip_stream, const pp_sensor_cfg* sensor_sets, pp_sensor* sstate) {
+    if (!sensor_sets || !sstate) return PP_ERR_ARG;
+    return sweep_impl(M, sets, cfg, ecfg, jcfg, fcfg, lcfg, tel, traffic, res, jstate, fstate, lstate, stats, device,
+                      hip_stream, sensor_sets, sstate);
 }
 
 }  // extern "C"

@@ -466,6 +466,25 @@ bool lane_change_ok(const pp_lane_change_cfg* c, const pp_lane_change* l) {
            l->home && l->wait && l->changes && l->arc && l->gain && l->dir;
 }
 
+// the sensor's configuration in range and every array of its state (the row arrays where rows > 0)
+bool sensor_ok(const pp_sensor_cfg* c, const pp_sensor* x, int32_t rows) {
+    if (!c || !x || !ppsensor::cfg_ok(*c) || !x->frame || !x->n_cars) return false;
+    return rows == 0 || (x->car_id && x->car_x && x->car_y && x->car_vx && x->car_vy && x->fate);
+}
+
+// what the sensor reads of a frame: the ego's position and the car rows
+bool sense_frame_ok(const pp_scene_batch* tel) {
+    if (!tel || tel->n_scenes < 0 || tel->car_stride < 0 || tel->car_stride > PP_MAX_CARS || !tel->ego_x ||
+        !tel->ego_y || !tel->n_cars)
+        return false;
+    return tel->car_stride == 0 || (tel->car_id && tel->car_x && tel->car_y && tel->car_vx && tel->car_vy);
+}
+
+ppsensor::Truth truth_view(const pp_scene_batch* b) {
+    return {b->n_scenes, b->car_stride, b->ego_x, b->ego_y, b->n_cars, b->car_id, b->car_x, b->car_y, b->car_vx,
+            b->car_vy};
+}
+
 ppsynth::TrafficV traffic_view(const pp_traffic* t, int64_t S) {
     ppsynth::TrafficV v;
     v.S = S; v.n = t->n_cars; v.lane = t->lane; v.seg = t->seg; v.t = t->t; v.off = t->offset; v.v = t->speed;

@@ -1,5 +1,5 @@
 // pp_k_world.h — device: what surrounds the evaluator. The closed-loop rollout's simulator shim, judge
-// and car-following, lane-changing traffic (k_sim, k_judge, k_follow, k_lane_change), the judge summary (k_summary_*), scene synthesis (k_synth*), the map tables'
+// and car-following, lane-changing traffic (k_sim, k_judge, k_follow, k_lane_change), the sensor model (k_sense), the judge summary (k_summary_*), scene synthesis (k_synth*), the map tables'
 // kernels (Map::Init, src/main.cpp:89-131) and k_libm. Part of pp_eval.hip's translation unit.
 #pragma once
 
@@ -126,6 +126,16 @@ __global__ __launch_bounds__(256) void k_lane_change(ppsynth::LaneTables LT, ppf
     if (s >= S) return;
     pplanechange::lane_change_scene(LT, AT, S, s, ego_x[s], ego_y[s], ego_speed_mph[s], tr, consume, fcfg, fst, cfg,
                                     st);
+}
+
+// The sensor model (include/pp.h pp_sense_frame; csrc/pp_sensor.h): one lane per scene, every array
+// [r * S + s]; no LDS, no per-lane arrays. Reads the telemetry's ego position and car rows (the truth),
+// so in a rollout it runs before pp_eval; writes only the sensor state. The occlusion loop reads the
+// truth rows again from global memory (contiguous across the wave, served by L1/L2).
+__global__ __launch_bounds__(256) void k_sense(ppsensor::Truth T, pp_sensor_cfg cfg, pp_sensor st) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= T.S) return;
+    ppsensor::sense_scene(T, s, cfg, st);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -159,6 +159,23 @@ class LaneChange(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in LANE_CHANGE_FIELDS]
 
 
+class SensorCfg(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("first_scene", C.c_int64), ("pos_sigma", C.c_double),
+                ("pos_sigma_per_m", C.c_double), ("vel_sigma", C.c_double), ("dropout_prob", C.c_double),
+                ("occlusion_radius", C.c_double)]
+
+
+# the sensor model's state (include/pp.h pp_sensor); "r": [car_stride, S], one row per telemetry row
+SENSE_NONE, SENSE_REPORTED, SENSE_OCCLUDED, SENSE_DROPPED = range(4)
+SENSOR_FIELDS = [("frame", "i4", None), ("n_cars", "i4", None), ("car_id", "i4", "n"), ("car_x", "f8", "n"),
+                 ("car_y", "f8", "n"), ("car_vx", "f8", "n"), ("car_vy", "f8", "n"), ("fate", "i4", "n")]
+SENSED_ROWS = ["n_cars", "car_id", "car_x", "car_y", "car_vx", "car_vy"]      # what replaces the truth's for pp_eval
+
+
+class Sensor(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _, _ in SENSOR_FIELDS]
+
+
 class EpisodeCfg(C.Structure):
     _fields_ = [("n_cars", C.c_int32), ("_pad", C.c_int32), ("ego_speed_min", C.c_double),
                 ("ego_speed_max", C.c_double), ("car_speed_min", C.c_double), ("car_speed_max", C.c_double),
@@ -226,7 +243,8 @@ class Result(C.Structure):
                 ("draw_mean_cost", C.c_void_p)]
 
 
-# exported symbols of include/pp.h (checked by tests/test_capi.py)
+# exported symbols of include/pp.h (checked by tests/test_capi.py; pp_sensor_word, the one function that
+# returns a uint32_t, is bound below as well)
 EXPORTS = ["pp_params_default", "pp_num_candidates", "pp_version", "pp_map_create",
            "pp_map_destroy", "pp_map_geometry", "pp_reserve", "pp_eval", "pp_plan_frame",
            "pp_synth_scenes", "pp_synth_scenes_host", "pp_timing_enable", "pp_timing_read",
@@ -238,7 +256,9 @@ EXPORTS = ["pp_params_default", "pp_num_candidates", "pp_version", "pp_map_creat
            "pp_follow_cfg_default", "pp_traffic_follow", "pp_traffic_follow_host", "pp_rollout_reactive",
            "pp_episode_cfg_default", "pp_synth_episode", "pp_synth_episode_host", "pp_math_eval",
            "pp_lane_change_cfg_default", "pp_traffic_lane_change", "pp_traffic_lane_change_host",
-           "pp_rollout_lane_changing", "pp_judge_summary", "pp_judge_summary_host", "pp_rollout_sweep"]
+           "pp_rollout_lane_changing", "pp_judge_summary", "pp_judge_summary_host", "pp_rollout_sweep",
+           "pp_sensor_cfg_default", "pp_sense_frame", "pp_sense_frame_host", "pp_sensor_gauss", "pp_rollout_sensed",
+           "pp_rollout_sweep_sensed"]
 
 
 def _load():
@@ -337,6 +357,21 @@ def _load():
                                      C.POINTER(Follow), C.POINTER(LaneChange), C.POINTER(JudgeStats), C.c_int32,
                                      C.c_void_p]
     lib.pp_rollout_sweep.restype = C.c_int32
+    lib.pp_sensor_cfg_default.argtypes = [C.POINTER(SensorCfg)]
+    lib.pp_sensor_cfg_default.restype = None
+    lib.pp_sense_frame.argtypes = [C.POINTER(SceneBatch), C.POINTER(SensorCfg), C.POINTER(Sensor), C.c_int32,
+                                   C.c_void_p]
+    lib.pp_sense_frame.restype = C.c_int32
+    lib.pp_sense_frame_host.argtypes = [C.POINTER(SceneBatch), C.POINTER(SensorCfg), C.POINTER(Sensor)]
+    lib.pp_sense_frame_host.restype = C.c_int32
+    lib.pp_sensor_gauss.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
+    lib.pp_sensor_gauss.restype = C.c_double
+    lib.pp_sensor_word.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int32]
+    lib.pp_sensor_word.restype = C.c_uint32
+    lib.pp_rollout_sensed.argtypes = lib.pp_rollout_lane_changing.argtypes + [C.POINTER(SensorCfg), C.POINTER(Sensor)]
+    lib.pp_rollout_sensed.restype = C.c_int32
+    lib.pp_rollout_sweep_sensed.argtypes = lib.pp_rollout_sweep.argtypes + [C.POINTER(SensorCfg), C.POINTER(Sensor)]
+    lib.pp_rollout_sweep_sensed.restype = C.c_int32
     lib.pp_synth_traffic.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.POINTER(SceneBatch),
                                      C.POINTER(Traffic), C.c_int32, C.c_void_p]
     lib.pp_synth_traffic.restype = C.c_int32
@@ -824,6 +859,64 @@ def rollout_lane_changing(m, scenes, traffic, prm, result, follow, lane_change, 
              fcfg if fcfg is not None else default_follow_cfg(), follow_struct(follow), *change)
 
 
+def default_sensor_cfg(**over) -> SensorCfg:
+    """pp_sensor_cfg_default (the identity sensor), with fields overridden by keyword."""
+    return _default_cfg(SensorCfg, lib.pp_sensor_cfg_default, over)
+
+
+def alloc_sensor(S, car_stride=12, xp="numpy", device=None):
+    """Zero-filled sensor state of S scenes x car_stride rows (every scene a fresh episode)."""
+    return _alloc_state(SENSOR_FIELDS, S, car_stride, xp, device)
+
+
+def sensor_struct(x) -> Sensor:
+    return _struct(Sensor, [k for k, _, _ in SENSOR_FIELDS], x)
+
+
+def sensor_to_numpy(x):
+    return _to_numpy(x)
+
+
+def sensed_scenes(scenes, sensor):
+    """The scene dict pp_eval is handed behind a sensor: `scenes` with the sensor state's rows in place
+    of the truth's (the other arrays, the car table among them, shared)."""
+    return dict(scenes, **{k: sensor[k] for k in SENSED_ROWS})
+
+
+def sense_frame(scenes, sensor, cfg=None, host=None, device=0, stream=None):
+    """pp_sense_frame / pp_sense_frame_host: one frame of the sensor model from the scenes' ego position
+    and car rows (the truth, only read); `sensor` is updated in place. host=None picks the host twin
+    when the arrays are numpy."""
+    if host is None:
+        host = isinstance(scenes["ego_x"], np.ndarray)
+    cfg = cfg if cfg is not None else default_sensor_cfg()
+    b = scene_struct(scenes)
+    assert sensor["fate"].shape[0] >= b.car_stride, "sensor state holds fewer rows than the scenes' car_stride"
+    X = sensor_struct(sensor)
+    if host:
+        _check(lib.pp_sense_frame_host(_ref(b), _ref(cfg), _ref(X)), "pp_sense_frame_host")
+    else:
+        _check(lib.pp_sense_frame(_ref(b), _ref(cfg), _ref(X), device, stream), "pp_sense_frame")
+
+
+def rollout_sensed(m, scenes, traffic, prm, result, follow, lane_change, sensor, n_frames, consume=3,
+                   sensor_range=300.0, log=None, judge=None, jcfg=None, fcfg=None, lcfg=None, scfg=None, device=0,
+                   stream=None):
+    """pp_rollout_sensed: rollout_lane_changing() whose planner sees the traffic through the sensor model
+    (sensor state updated in place); everything else reads the truth. scfg=None: the identity sensor."""
+    n = int(traffic["n_cars"])
+    assert follow["desired"].shape[0] >= n, "follow state holds fewer cars than the traffic"
+    assert sensor["fate"].shape[0] >= int(scenes["car_id"].shape[0]), "sensor state holds fewer rows than the scenes"
+    change = (None, None)
+    if lane_change is not None:
+        assert lane_change["home"].shape[0] >= n, "lane-change state holds fewer cars than the traffic"
+        change = (lcfg if lcfg is not None else default_lane_change_cfg(), lane_change_struct(lane_change))
+    _rollout(lib.pp_rollout_sensed, "pp_rollout_sensed", m, scenes, traffic, prm, result, n_frames, consume,
+             sensor_range, log, device, stream, *_judge_stage(judge, jcfg),
+             fcfg if fcfg is not None else default_follow_cfg(), follow_struct(follow), *change,
+             scfg if scfg is not None else default_sensor_cfg(), sensor_struct(sensor))
+
+
 def alloc_judge_stats(rows, bins=64, xp="numpy", device=None):
     """Zero arrays for `rows` rows of summary figures with a histogram of `bins` bins (pp_judge_stats)."""
     mk = _zeros(xp, device)
@@ -903,13 +996,15 @@ def stats_quantile(stats, row, q, hist_max=HIST_MAX_DEFAULT):
 
 def rollout_sweep(m, sets, S, n_frames, scenes_per_group=None, seed=0x5EED0001, first=0, consume=3,
                   sensor_range=300.0, hist_bins=64, hist_max=HIST_MAX_DEFAULT, ecfg=None, jcfg=None, fcfg=None,
-                  lcfg=None, lane_changes=True, device=0, stream=None, buffers=None):
+                  lcfg=None, lane_changes=True, device=0, stream=None, buffers=None, sensors=None, sensor=None):
     """pp_rollout_sweep: drives the same S seeded episodes (synth_episode) once per parameter set of
     `sets` (a list of Params) through rollout_lane_changing and summarises each drive per group of
     `scenes_per_group` scenes (None: S), all on the one stream with no host synchronisation. Returns
     (stats, buffers): the dict of device arrays of len(sets) * G rows, set p's group g in row p * G +
     g, and the drive's buffers (scenes, traffic, result, judge, follow, lane_change: the last set's end
-    state), which a later call of the same sizes may pass back in."""
+    state), which a later call of the same sizes may pass back in. `sensors` (a list of SensorCfg, one per
+    set): pp_rollout_sweep_sensed, set p driven through rollout_sensed with sensors[p]; `sensor` is its
+    state (None: allocated; buffers["sensor"] either way)."""
     import torch
     dev = torch.device("cuda", device)
     ecfg = ecfg if ecfg is not None else default_episode_cfg()
@@ -938,9 +1033,19 @@ def rollout_sweep(m, sets, S, n_frames, scenes_per_group=None, seed=0x5EED0001, 
                    SummaryCfg(E, hist_bins, 0, float(hist_max), 0, 0))
     b, T, R = scene_struct(buffers["scenes"]), traffic_struct(buffers["traffic"]), result_struct(buffers["result"])
     J, F, O = judge_struct(buffers["judge"]), follow_struct(buffers["follow"]), stats_struct(stats)
-    _check(lib.pp_rollout_sweep(m.handle, arr, _ref(cfg), _ref(ecfg), _ref(jcfg), _ref(fcfg),
-                                _ref(lcfg) if lc is not None else None, _ref(b), _ref(T), _ref(R), _ref(J), _ref(F),
-                                _ref(L), _ref(O), device, stream), "pp_rollout_sweep")
+    args = (m.handle, arr, _ref(cfg), _ref(ecfg), _ref(jcfg), _ref(fcfg), _ref(lcfg) if lc is not None else None,
+            _ref(b), _ref(T), _ref(R), _ref(J), _ref(F), _ref(L), _ref(O), device, stream)
+    if sensors is None:
+        _check(lib.pp_rollout_sweep(*args), "pp_rollout_sweep")
+    else:
+        assert len(sensors) == P, "one sensor per parameter set"
+        if sensor is None:
+            sensor = buffers.get("sensor")
+        if sensor is None:
+            sensor = alloc_sensor(S, int(buffers["scenes"]["car_id"].shape[0]), xp="torch", device=dev)
+        buffers["sensor"] = sensor
+        sarr = (SensorCfg * max(P, 1))(*sensors)
+        _check(lib.pp_rollout_sweep_sensed(*args, sarr, _ref(sensor_struct(sensor))), "pp_rollout_sweep_sensed")
     buffers["traffic"]["n_cars"] = int(ecfg.n_cars)
     return stats, buffers
 

@@ -661,6 +661,91 @@ int32_t pp_rollout_sweep(pp_map* m, const pp_params* sets, const pp_sweep_cfg* c
                          pp_result* result, pp_judge* jstate, pp_follow* fstate, pp_lane_change* lstate,
                          pp_judge_stats* stats, int32_t device, void* hip_stream);
 
+/* ---- sensor model: what the planner is told about the traffic ---------------------------------- */
+/* The simulator reports every car within sensor_range at its exact position and velocity. The sensor
+ * model stands between that TRUTH and the planner: a car may be hidden behind a nearer car, a report
+ * may be lost, and what is reported carries noise. THIS LIBRARY'S OWN definitions (DESIGN.md "Sensor
+ * model" states them in full). The truth is `telemetry`'s ego_x, ego_y, n_cars and car rows, which
+ * are only read; the sensed rows go to the state's own arrays, compacted in truth order. Per truth
+ * row r (car id j, centre c), with a = c - ego, f = frame[s] before the call, gs = first_scene + s:
+ *   occluded  (occlusion_radius > 0) some truth row k != r with b = c_k - ego has b.b < a.a and
+ *             |b - u a|^2 <= occlusion_radius^2, u = (a.b) / (a.a) clamped to [0, 1]. Every truth row
+ *             can occlude, whatever its own fate; O(rows^2) per scene
+ *   dropped   (not occluded) (double)w 2^-32 < dropout_prob, w = pp_sensor_word(seed, gs, f, j)
+ *   reported  x + sp g0, y + sp g1, vx + vel_sigma g2, vy + vel_sigma g3 with sp = pos_sigma +
+ *             pos_sigma_per_m sqrt(a.a) and g_q = pp_sensor_gauss(seed, gs, f, j, q); a field whose
+ *             sigma is exactly 0 is copied (sp is 0 where both its coefficients are, whatever a.a)
+ * Afterwards frame[s] = f + 1. A car's draws depend on (seed, gs, f, j) only: shards concatenate. */
+#define PP_SENSE_NONE      0   /* fate of a row r >= n_cars[s]: no truth row                       */
+#define PP_SENSE_REPORTED  1
+#define PP_SENSE_OCCLUDED  2
+#define PP_SENSE_DROPPED   3
+
+typedef struct pp_sensor_cfg {
+    uint64_t seed;
+    int64_t  first_scene;          /* global index of the batch's scene 0 (shards), >= 0            */
+    double   pos_sigma;            /* 0 m: position noise at the ego                                */
+    double   pos_sigma_per_m;      /* 0: position noise added per metre of distance                 */
+    double   vel_sigma;            /* 0 m/s                                                         */
+    double   dropout_prob;         /* 0: probability that a visible car is not reported, in [0, 1]  */
+    double   occlusion_radius;     /* 0 m: off                                                      */
+} pp_sensor_cfg;                   /* sigmas and radius finite and >= 0; the default: the identity  */
+
+/* Sensor state of a batch (SoA, caller owned; device resident for pp_sense_frame and
+ * pp_rollout_sensed, host memory for pp_sense_frame_host), S = the telemetry's n_scenes; row arrays
+ * [r * S + s] for r < the telemetry's car_stride. A zero `frame` is a fresh episode and a state is
+ * reused by zeroing `frame` alone. Every fate entry is written by every call; sensed rows at and
+ * beyond n_cars[s] are not. */
+typedef struct pp_sensor {
+    int32_t* frame;                /* carried: frames sensed so far in the episode                  */
+    int32_t* n_cars;               /* sensed rows                                                   */
+    int32_t* car_id;               /* the sensed rows, in truth order (ascending id)                */
+    double*  car_x;
+    double*  car_y;
+    double*  car_vx;
+    double*  car_vy;
+    int32_t* fate;                 /* per TRUTH row r: PP_SENSE_*                                   */
+} pp_sensor;
+
+void    pp_sensor_cfg_default(pp_sensor_cfg* c);
+/* Senses ONE frame from the telemetry alone (no map), for callers with their own loop: hand pp_eval a
+ * copy of the telemetry struct whose n_cars and car_* are the state's. Writes `state` only. PP_ERR_ARG
+ * (before any HIP call) for a NULL argument or array, a sigma or radius that is negative or not
+ * finite, a probability outside [0, 1], first_scene < 0, n_scenes < 0 or a car_stride outside
+ * 0..PP_MAX_CARS. Device pointers; asynchronous on hip_stream. */
+int32_t pp_sense_frame(const pp_scene_batch* telemetry, const pp_sensor_cfg* cfg, pp_sensor* state,
+                       int32_t device, void* hip_stream);
+/* The same on the host (host pointers; the same arithmetic, bit for bit). */
+int32_t pp_sense_frame_host(const pp_scene_batch* telemetry, const pp_sensor_cfg* cfg, pp_sensor* state);
+/* The draws restated on the host (bit-identical to the device's): Gaussian q = 0..3 (x, y, vx, vy)
+ * and the dropout word of car `car` in frame `frame` of global scene `scene`. Philox4x32-10, key =
+ * seed, counter = {scene lo, scene hi, (frame PP_NOISE_CAR_STRIDE + car) 8 + q, 0x53454E53} (mod 2^32;
+ * the dropout block is q = 4, its word 0); the Gaussian is pp_mc_gauss's Irwin-Hall unit. */
+double  pp_sensor_gauss(uint64_t seed, int64_t scene, int32_t frame, int32_t car, int32_t q);
+uint32_t pp_sensor_word(uint64_t seed, int64_t scene, int32_t frame, int32_t car);
+/* pp_rollout_lane_changing with the sensor: a frame begins with the sensor on the telemetry, pp_eval
+ * plans from the sensed rows (and updates the telemetry's car table from them, so a car that is not
+ * reported keeps its stale entry), and the follow update, the lane changes, the judge and the
+ * simulator read and write the truth as before. The log's n_cars is the truth's. scfg and sstate both
+ * NULL: exactly pp_rollout_lane_changing; one alone is refused. */
+int32_t pp_rollout_sensed(pp_map* m, pp_scene_batch* telemetry, pp_traffic* traffic,
+                          const pp_params* prm, const pp_rollout_cfg* cfg, pp_result* result,
+                          pp_rollout_log* log, int32_t device, void* hip_stream,
+                          const pp_judge_cfg* jcfg, pp_judge* jstate,
+                          const pp_follow_cfg* fcfg, pp_follow* fstate,
+                          const pp_lane_change_cfg* lcfg, pp_lane_change* lstate,
+                          const pp_sensor_cfg* scfg, pp_sensor* sstate);
+/* pp_rollout_sweep with a sensor per set: set p is driven with sets[p] and sensor_sets[p] (host
+ * memory, n_sets entries). Per set the steps are pp_rollout_sweep's, but sstate->frame is zeroed on
+ * the stream before the drive, and the drive is pp_rollout_sensed. Every set is checked before the
+ * first launch. */
+int32_t pp_rollout_sweep_sensed(pp_map* m, const pp_params* sets, const pp_sweep_cfg* cfg,
+                                const pp_episode_cfg* ecfg, const pp_judge_cfg* jcfg, const pp_follow_cfg* fcfg,
+                                const pp_lane_change_cfg* lcfg, pp_scene_batch* telemetry, pp_traffic* traffic,
+                                pp_result* result, pp_judge* jstate, pp_follow* fstate, pp_lane_change* lstate,
+                                pp_judge_stats* stats, int32_t device, void* hip_stream,
+                                const pp_sensor_cfg* sensor_sets, pp_sensor* sstate);
+
 /* A batch in HOST memory (the batched onMessage; what a server calls per tick): stages the
  * scenes — and their car table when tab_valid is set, updated in place — through device memory,
  * runs pp_eval on hip_stream and copies winner, n_out, next_x/next_y, cost and status back into
