@@ -736,7 +736,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kW4 ? 4 : k
 // rows r, r + G, ... (coalesced across the group) and scans every G-th waypoint for the Frenet
 // frame; the planner's pass then runs over each round's G cars in ascending row order on every
 // lane of the group (the cars' Frenet states exchanged by lane shuffles), i.e. in the reference's
-// own iteration order. No car table (pp_eval picks k_prep for table mode).
+// own iteration order. With a car table the group's lanes take its slots the same way (slot r,
+// r + G, ...; prep_grp_eval below): eval_plan never forces one lane per scene for table mode.
 // One evaluation v by the G lanes of a group (this one is lane r); every lane of the group runs it
 template <int G>
 __device__ __forceinline__ void prep_grp_eval(const MapV& m, const pp_scene_batch& in, const pp_params& P,
