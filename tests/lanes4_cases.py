@@ -97,6 +97,20 @@ class TestFourLanesGPU:
         assert (got["winner"] // prm.n_speeds == 3).sum() > 50
         print(f"4 lanes, mode {mode}: {S} scenes x {got['cost'].shape[1]} candidates, max |dxy| {e:.2e} m")
 
+    @pytest.mark.parametrize("mode", [ppamd.COST_REFERENCE, ppamd.COST_COMFORT])
+    def test_slow_route_vs_restatement(self, env, mode):
+        """The checked K2 route at four lanes: wound-up headings on every rung and speed-edge scenes
+        (tests/slow_route_lib.py), reference mode without paths and comfort mode, evaluated twice
+        back to back, against the restatement with the heading bound."""
+        import slow_route_lib as srl
+        import test_slow_route as tsr
+        S = 600
+        sc, meta = srl.mixed_slow_scenes(env["m"], S, seed=4410, first=4410)
+        prm = ppamd.default_params(cost_mode=mode)
+        got = tsr.ev(env, tsr.to_dev(env, sc), prm)
+        assert (got["status"] != 0).any()
+        tsr.oracle_check(env, sc, meta, got, prm, what=f"4 lanes, slow route, mode {mode}")
+
     def test_device_map_init(self, env):
         t = env["torch"]
         wx = t.from_numpy(env["wx"]).to(env["dev"])

@@ -13,6 +13,7 @@ import pytest
 
 import oracle_lib
 from oracle_lib import ppamd
+from slow_route_lib import speed_edge_scenes
 
 pytestmark = pytest.mark.gpu
 SPB = 17                        # scenes per k_cand group at the default 15 candidates
@@ -68,31 +69,6 @@ def on_off(env, sc, prm=None):
     assert ppamd.debug_get(ppamd.DBG_LAST_PERSIST) == 0
     assert_same_bits(a, b)
     return a, b
-
-
-def speed_edge_scenes(m, S, seed=909, first=31337):
-    """test_gpu_parity.py::test_speed_range_edges_vs_oracle's scenes: two of three are frame-0 scenes
-    whose telemetry speed is -0, subnormal, tiny, huge or negative, and every other scene has a car
-    just ahead whose velocity is 0, -0, subnormal or tiny, so k_prep flags kLimSlow scenes all
-    through the batch and flagged groups interleave with fast ones."""
-    sc = ppamd.synth_host(m, S, seed=seed, first=first)
-    speeds = [-0.0, 0.0, 5e-324, 1e-310, 1e-300, 1e-40, 1e-18, 2.237e-17, 1e-12, 1e-6, 0.3,
-              49.66, 3e6, 1e300, -3.0, -1e-300, 2.237 * 22.2]
-    vels = [0.0, -0.0, 5e-324, 1e-300, 1e-25, 1e-9, 3.0]
-    p9x, p9y = sc["prev_x"][9], sc["prev_y"][9]
-    hx, hy = p9x - sc["prev_x"][8], p9y - sc["prev_y"][8]
-    nrm = np.maximum(np.hypot(hx, hy), 1e-12)
-    for s in range(S):
-        if s % 3 != 2:
-            sc["n_prev"][s] = 0
-            sc["ego_speed_mph"][s] = speeds[s % len(speeds)]
-        if s % 2 == 0:
-            sc["car_x"][0, s] = p9x[s] + hx[s] / nrm[s] * 20.0
-            sc["car_y"][0, s] = p9y[s] + hy[s] / nrm[s] * 20.0
-            v = vels[(s // 2) % len(vels)]
-            sc["car_vx"][0, s] = v
-            sc["car_vy"][0, s] = v
-    return sc
 
 
 def test_three_groups_vs_oracle(env):

@@ -11,7 +11,8 @@ import pytest
 
 import oracle_lib
 from oracle_lib import ppamd
-from test_persist import SPB, assert_same_bits, run, speed_edge_scenes, to_dev
+from slow_route_lib import speed_edge_scenes
+from test_persist import SPB, assert_same_bits, run, to_dev
 
 pytestmark = pytest.mark.gpu
 OFFS8 = [-6, -4, -3, -2, -1, 0, 2]      # bench.py's offsets at n_speeds = 8

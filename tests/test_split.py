@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle_lib
+import slow_route_lib
 from oracle_lib import ppamd
 
 pytestmark = pytest.mark.gpu
@@ -46,6 +47,7 @@ def run(env, sc, prm, mode, group=0):
 def test_split_bit_identical(env, S, mode, parts, group):
     sc = ppamd.synth_host(env["m"], S, seed=S, first=S)
     idx = np.arange(7, S, 211)                    # speed-edge scenes: k_cand<true> groups in both halves
+    sc["n_prev"][idx] = 0                         # (frame-0 scenes: only they read the telemetry speed)
     sc["ego_speed_mph"][idx] = np.array([-0.0, 5e-324, 3e6, -3.0])[np.arange(len(idx)) % 4]
     prm = ppamd.default_params()
     a = run(env, sc, prm, mode, group)
@@ -57,9 +59,10 @@ def test_split_bit_identical(env, S, mode, parts, group):
         assert (x.view(np.uint8) == y.view(np.uint8)).all(), k
     edges = [S * k // d for d in (2, 3, 6) for k in range(1, d)]     # part and chunk boundaries
     sub = np.unique(np.concatenate([np.arange(0, min(300, S)), np.arange(max(S - 300, 0), S)] +
-                                   [np.arange(max(e - 150, 0), min(e + 150, S)) for e in edges]))
+                                   [np.arange(max(e - 150, 0), min(e + 150, S)) for e in edges] + [idx]))
     part = {k: np.ascontiguousarray(v[..., sub]) for k, v in sc.items()}
-    ref = oracle_lib.oracle_eval(env["olib"], env["wx"], env["wy"], part, prm, info=False)
+    ref = oracle_lib.oracle_eval(env["olib"], env["wx"], env["wy"], part, prm, info=True)
+    slow_route_lib.assert_effective(ref.pop("info"), part, np.searchsorted(sub, idx))
     got = {k: (v[:, sub] if k in ("next_x", "next_y") else v[sub]) for k, v in a.items()}
     oracle_lib.compare(got, ref)
 
@@ -87,6 +90,7 @@ def test_sort_cars_prepass_bit_identical(env, S, draws, mode):
     t = env["torch"]
     sc = ppamd.synth_host(env["m"], S, seed=S + 7, first=S)
     idx = np.arange(5, S, 307)
+    sc["n_prev"][idx] = 0                          # frame-0 scenes: only they read the telemetry speed
     sc["ego_speed_mph"][idx] = np.array([-0.0, 5e-324, 3e6, -3.0])[np.arange(len(idx)) % 4]
     sc["car_id"][3, idx[::3]] = -1                 # the 'no car' sentinel: identity order
     sc["n_cars"][idx[1::5]] = 1                   # one row: no sort
@@ -102,3 +106,13 @@ def test_sort_cars_prepass_bit_identical(env, S, draws, mode):
     for k in out[1]:
         a, b = np.asarray(out[1][k]), np.asarray(out[2][k])
         assert (a.view(np.uint8) == b.view(np.uint8)).all(), k
+    # every edge scene against the oracle: the scene info (draw 0: no noise) in every case, the
+    # whole result where there are no draws (a draw's noise is keyed by the scene's index in its
+    # batch, so a subset of a Monte-Carlo batch is no batch of its own)
+    part = {k: np.ascontiguousarray(v[..., idx]) for k, v in sc.items()}
+    ref = oracle_lib.oracle_eval(env["olib"], env["wx"], env["wy"], part, ppamd.default_params(), info=True)
+    slow_route_lib.assert_effective(ref["info"], part, np.arange(len(idx)))
+    got = {k: (v[:, idx] if k in ("next_x", "next_y") else v[idx]) for k, v in out[1].items()}
+    oracle_lib.compare_info(got["info"], ref["info"])
+    if draws == 0:
+        oracle_lib.compare({k: v for k, v in got.items() if k != "info"}, {k: v for k, v in ref.items() if k != "info"})

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import oracle_lib
+import slow_route_lib
 from oracle_lib import ppamd
 
 pytestmark = pytest.mark.gpu
@@ -29,6 +30,7 @@ def test_step_block_shapes_vs_oracle(env, S):
     t = env["torch"]
     sc = ppamd.synth_host(env["m"], S, seed=S + 17, first=S * 3)
     idx = np.arange(2, S, 37)
+    sc["n_prev"][idx] = 0                          # frame-0 scenes: only they read the telemetry speed
     sc["ego_speed_mph"][idx] = np.array([-0.0, 5e-324, 3e6, -3.0])[np.arange(len(idx)) % 4]
     prm = ppamd.default_params()
     d = {k: t.from_numpy(np.ascontiguousarray(v)).to(env["dev"]) for k, v in sc.items()}
@@ -41,8 +43,9 @@ def test_step_block_shapes_vs_oracle(env, S):
         sub = np.arange(S)
     else:
         edges = np.concatenate([np.arange(b - 2, b + 2) for b in range(8, S, 8)])
-        sub = np.unique(np.concatenate([edges[(edges >= 0) & (edges < S)][::7], np.arange(0, S, 13), [S - 1]]))
+        sub = np.unique(np.concatenate([edges[(edges >= 0) & (edges < S)][::7], np.arange(0, S, 13), [S - 1], idx]))
     part = {k: np.ascontiguousarray(v[..., sub]) for k, v in sc.items()}
-    ref = oracle_lib.oracle_eval(env["olib"], env["wx"], env["wy"], part, prm, info=False)
+    ref = oracle_lib.oracle_eval(env["olib"], env["wx"], env["wy"], part, prm, info=True)
+    slow_route_lib.assert_effective(ref.pop("info"), part, np.searchsorted(sub, idx))
     sel = {k: (v[:, sub] if k in ("next_x", "next_y") else v[sub]) for k, v in got.items()}
     oracle_lib.compare(sel, ref)
