@@ -1,5 +1,5 @@
 // pp_api_rollout.h — host: closed-loop rollouts, the judge, reactive traffic, the sensor model, the
-// judge summary and parameter sweeps (C ABI).
+// tracker, the judge summary and parameter sweeps (C ABI).
 // Part of pp_eval.hip's translation unit.
 #pragma once
 
@@ -26,6 +26,21 @@ int launch_lane_change(const WorldTables& W, const pp_scene_batch* tel, const pp
 
 int launch_sense(const pp_scene_batch* tel, const pp_sensor_cfg* sc, const pp_sensor* ss, void* stream) {
     return launch_scenes(k_sense, tel->n_scenes, stream, truth_view(tel), *sc, *ss);
+}
+
+int launch_track(const pp_scene_batch* seen, const pp_tracker_cfg* tc, int32_t consume, const pp_tracker* ts,
+                 void* stream) {
+    return launch_scenes(k_track, seen->n_scenes, stream, truth_view(seen), *tc, consume * 0.02, *ts);
+}
+
+// `b` with the rows of a sensor or tracker state in place of its own (the other arrays shared)
+template <class State>
+pp_scene_batch with_rows(const pp_scene_batch& b, const State& x) {
+    pp_scene_batch v = b;
+    v.n_cars = x.n_cars; v.car_id = x.car_id;
+    v.car_x = x.car_x; v.car_y = x.car_y;
+    v.car_vx = x.car_vx; v.car_vy = x.car_vy;
+    return v;
 }
 
 // every argument check of pp_synth_episode and its host twin (no HIP call); *gap: the gap rule in force
@@ -63,6 +78,8 @@ struct Stages {
     const pp_lane_change* ls = nullptr;
     const pp_sensor_cfg* sc = nullptr;
     const pp_sensor* ss = nullptr;
+    const pp_tracker_cfg* tc = nullptr;
+    const pp_tracker* ts = nullptr;
 };
 
 // each stage asked for against its own arguments and what it reads of a frame; lane changes read the
@@ -70,10 +87,12 @@ struct Stages {
 bool stages_ok(const Stages& st, const pp_scene_batch* tel, const pp_traffic* traffic, const pp_result* res,
                int32_t consume) {
     const bool judge = st.jc || st.js, follow = st.fc || st.fs, change = st.lc || st.ls, sense = st.sc || st.ss;
+    const bool track = st.tc || st.ts;
     if (((st.need & kJudge) && !judge) || ((st.need & kFollow) && !follow)) return false;
     if (judge && (!judge_ok(st.jc, st.js) || !judge_frame_ok(tel, traffic, res, consume))) return false;
     if (follow && (!follow_ok(st.fc, st.fs) || !follow_frame_ok(tel, traffic, consume))) return false;
     if (sense && (!sense_frame_ok(tel) || !sensor_ok(st.sc, st.ss, tel->car_stride))) return false;
+    if (track && (!sense_frame_ok(tel) || !tracker_ok(st.tc, st.ts, tel->car_stride) || consume < 1)) return false;
     return !change || (follow && lane_change_ok(st.lc, st.ls));
 }
 
@@ -92,10 +111,12 @@ bool rollout_ok(const pp_map* M, const pp_scene_batch* tel, const pp_traffic* tr
     return !(log && log->plan_x && !log->plan_y);
 }
 
-// pp_rollout's loop, a frame in this order: k_sense, pp_eval, k_follow, k_lane_change (not without
-// cars), k_judge, k_sim, each of the four only where its stage is asked for. With the sensor pp_eval
-// plans from `seen`: the telemetry with the sensor state's rows in place of the truth's (the car table
-// is shared, so it is updated as before); every other stage reads and writes the truth.
+// pp_rollout's loop, a frame in this order: k_sense, k_track, pp_eval, k_follow, k_lane_change (not
+// without cars), k_judge, k_sim, each of the five only where its stage is asked for. With the sensor
+// `sensed` is the telemetry with the sensor state's rows in place of the truth's; with the tracker
+// pp_eval plans from `seen`, the telemetry with the tracker's rows (made from `sensed`), otherwise from
+// `sensed` itself (the car table is shared, so it is updated as before); every other stage reads and
+// writes the truth.
 int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
                      const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
                      void* hip_stream, const Stages& st) {
@@ -108,14 +129,11 @@ int32_t rollout_loop(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const 
     A.range2 = cfg->sensor_range * cfg->sensor_range;
     if (log) A.log = *log; else memset(&A.log, 0, sizeof(A.log));
     const ppsynth::TrafficV tv = traffic_view(traffic, tel->n_scenes);
-    pp_scene_batch seen = *tel;
-    if (st.ss) {
-        seen.n_cars = st.ss->n_cars; seen.car_id = st.ss->car_id;
-        seen.car_x = st.ss->car_x; seen.car_y = st.ss->car_y;
-        seen.car_vx = st.ss->car_vx; seen.car_vy = st.ss->car_vy;
-    }
+    const pp_scene_batch sensed = st.ss ? with_rows(*tel, *st.ss) : *tel;
+    const pp_scene_batch seen = st.ts ? with_rows(*tel, *st.ts) : sensed;
     for (int f = 0; f < cfg->n_frames; f++) {
         int rc = st.ss ? launch_sense(tel, st.sc, st.ss, hip_stream) : PP_OK;
+        if (rc == PP_OK && st.ts) rc = launch_track(&sensed, st.tc, cfg->consume, st.ts, hip_stream);
         if (rc == PP_OK) rc = pp_eval(M, &seen, prm, res, device, hip_stream);
         if (rc == PP_OK && st.fs) rc = launch_follow(W, tel, tv, cfg->consume, st.fc, st.fs, hip_stream);
         if (rc == PP_OK && st.ls && tv.n > 0)
@@ -339,6 +357,38 @@ int32_t pp_rollout_sensed(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, c
                         Stages{kFollow, jstate ? jcfg : nullptr, jstate, fcfg, fstate, lcfg, lstate, scfg, sstate});
 }
 
+void pp_tracker_cfg_default(pp_tracker_cfg* c) { if (c) pptracker::cfg_default(c); }
+
+int32_t pp_track_frame(const pp_scene_batch* seen, const pp_tracker_cfg* cfg, int32_t consume, pp_tracker* state,
+                       int32_t device, void* hip_stream) {
+    if (device < 0 || device >= kMaxDev || consume < 1 || !sense_frame_ok(seen) ||
+        !tracker_ok(cfg, state, seen->car_stride))
+        return PP_ERR_ARG;
+    if (seen->n_scenes == 0) return PP_OK;
+    DeviceGuard g(device);
+    return launch_track(seen, cfg, consume, state, hip_stream);
+}
+
+int32_t pp_track_frame_host(const pp_scene_batch* seen, const pp_tracker_cfg* cfg, int32_t consume,
+                            pp_tracker* state) {
+    if (consume < 1 || !sense_frame_ok(seen) || !tracker_ok(cfg, state, seen->car_stride)) return PP_ERR_ARG;
+    const ppsensor::Truth Z = truth_view(seen);
+    for (int64_t s = 0; s < Z.S; s++) pptracker::track_scene(Z, s, *cfg, consume * 0.02, *state);
+    return PP_OK;
+}
+
+// (a lone tcfg or a lone tstate asks for the tracker and is refused; neither: none)
+int32_t pp_rollout_tracked(pp_map* M, pp_scene_batch* tel, pp_traffic* traffic, const pp_params* prm,
+                           const pp_rollout_cfg* cfg, pp_result* res, pp_rollout_log* log, int32_t device,
+                           void* hip_stream, const pp_judge_cfg* jcfg, pp_judge* jstate, const pp_follow_cfg* fcfg,
+                           pp_follow* fstate, const pp_lane_change_cfg* lcfg, pp_lane_change* lstate,
+                           const pp_sensor_cfg* scfg, pp_sensor* sstate, const pp_tracker_cfg* tcfg,
+                           pp_tracker* tstate) {
+    return rollout_loop(M, tel, traffic, prm, cfg, res, log, device, hip_stream,
+                        Stages{kFollow, jstate ? jcfg : nullptr, jstate, fcfg, fstate, lcfg, lstate, scfg, sstate, tcfg,
+                               tstate});
+}
+
 void pp_episode_cfg_default(pp_episode_cfg* c) { if (c) ppepisode::cfg_default(c); }
 
 int32_t pp_synth_episode(pp_map* M, uint64_t seed, int64_t first_scene, const pp_episode_cfg* cfg,
@@ -396,12 +446,14 @@ int32_t pp_judge_summary_host(const pp_judge* state, int64_t n_scenes, const pp_
 namespace {
 // Every set is checked against every call of its round before the first launch; the rounds are then
 // the public entry points themselves, so a set's rows are what those calls made by hand produce.
-// sensors: a sensor per set and its state (pp_rollout_sweep_sensed), or both null (pp_rollout_sweep).
+// sensors: a sensor per set and its state (pp_rollout_sweep_sensed), or both null (pp_rollout_sweep);
+// trackers: the same for the tracker (pp_rollout_sweep_tracked).
 int32_t sweep_impl(pp_map* M, const pp_params* sets, const pp_sweep_cfg* cfg, const pp_episode_cfg* ecfg,
                    const pp_judge_cfg* jcfg, const pp_follow_cfg* fcfg, const pp_lane_change_cfg* lcfg,
                    pp_scene_batch* tel, pp_traffic* traffic, pp_result* res, pp_judge* jstate,
                    pp_follow* fstate, pp_lane_change* lstate, pp_judge_stats* stats, int32_t device,
-                   void* hip_stream, const pp_sensor_cfg* sensors, pp_sensor* sstate) {
+                   void* hip_stream, const pp_sensor_cfg* sensors, pp_sensor* sstate,
+                   const pp_tracker_cfg* trackers = nullptr, pp_tracker* tstate = nullptr) {
     pp_follow_cfg gap;
     if (!sets || !cfg || cfg->n_sets < 1 || !jstate || !fstate || device < 0 || device >= kMaxDev ||
         !episode_ok(M, cfg->first_scene, ecfg, fcfg, tel, traffic, jstate, fstate, &gap))
@@ -410,7 +462,8 @@ int32_t sweep_impl(pp_map* M, const pp_params* sets, const pp_sweep_cfg* cfg, co
     pp_traffic placed = *traffic;                       // as pp_synth_episode leaves it
     placed.n_cars = ecfg->n_cars;
     for (int p = 0; p < cfg->n_sets; p++) {
-        const Stages st{kFollow, jcfg, jstate, fcfg, fstate, lcfg, lstate, sensors ? &sensors[p] : nullptr, sstate};
+        const Stages st{kFollow, jcfg, jstate, fcfg, fstate, lcfg, lstate, sensors ? &sensors[p] : nullptr, sstate,
+                        trackers ? &trackers[p] : nullptr, tstate};
         if (!rollout_ok(M, tel, &placed, &sets[p], &cfg->rollout, res, nullptr, device, st) ||
             eval_check(M, tel, &sets[p], res, device) != PP_OK)
             return PP_ERR_ARG;
@@ -436,9 +489,15 @@ int32_t sweep_impl(pp_map* M, const pp_params* sets, const pp_sweep_cfg* cfg, co
             if (hipMemsetAsync(sstate->frame, 0, sizeof(int32_t) * (size_t)S, (hipStream_t)hip_stream) != hipSuccess)
                 rc = PP_ERR_HIP;
         }
+        if (rc == PP_OK && tstate) {
+            DeviceGuard g(device);
+            if (hipMemsetAsync(tstate->frame, 0, sizeof(int32_t) * (size_t)S, (hipStream_t)hip_stream) != hipSuccess)
+                rc = PP_ERR_HIP;
+        }
         if (rc == PP_OK)
-            rc = pp_rollout_sensed(M, tel, traffic, &sets[p], &cfg->rollout, res, nullptr, device, hip_stream, jcfg,
-                                   jstate, fcfg, fstate, lcfg, lstate, sensors ? &sensors[p] : nullptr, sstate);
+            rc = pp_rollout_tracked(M, tel, traffic, &sets[p], &cfg->rollout, res, nullptr, device, hip_stream, jcfg,
+                                    jstate, fcfg, fstate, lcfg, lstate, sensors ? &sensors[p] : nullptr, sstate,
+                                    trackers ? &trackers[p] : nullptr, tstate);
         sc.out_first = p * G;
         if (rc == PP_OK) rc = pp_judge_summary(M, jstate, S, &sc, stats, device, hip_stream);
         if (rc != PP_OK) return rc;
@@ -466,6 +525,17 @@ int32_t pp_rollout_sweep_sensed(pp_map* M, const pp_params* sets, const pp_sweep
     if (!sensor_sets || !sstate) return PP_ERR_ARG;
     return sweep_impl(M, sets, cfg, ecfg, jcfg, fcfg, lcfg, tel, traffic, res, jstate, fstate, lstate, stats, device,
                       hip_stream, sensor_sets, sstate);
+}
+
+int32_t pp_rollout_sweep_tracked(pp_map* M, const pp_params* sets, const pp_sweep_cfg* cfg, const pp_episode_cfg* ecfg,
+                                 const pp_judge_cfg* jcfg, const pp_follow_cfg* fcfg, const pp_lane_change_cfg* lcfg,
+                                 pp_scene_batch* tel, pp_traffic* traffic, pp_result* res, pp_judge* jstate,
+                                 pp_follow* fstate, pp_lane_change* lstate, pp_judge_stats* stats, int32_t device,
+                                 void* hip_stream, const pp_sensor_cfg* sensor_sets, pp_sensor* sstate,
+                                 const pp_tracker_cfg* tracker_sets, pp_tracker* tstate) {
+    if (!sensor_sets || !sstate || !tracker_sets || !tstate) return PP_ERR_ARG;
+    return sweep_impl(M, sets, cfg, ecfg, jcfg, fcfg, lcfg, tel, traffic, res, jstate, fstate, lstate, stats, device,
+                      hip_stream, sensor_sets, sstate, tracker_sets, tstate);
 }
 
 }  // extern "C"

@@ -23,7 +23,7 @@
 // device resources and the world stages' tables and per-scene launch (pp_host_map.h), pp_eval's
 // launches (pp_launch.h), the C ABI (pp_api.h, pp_api_rollout.h, pp_api_frame.h). The world stages'
 // shared arithmetic and default configurations are pp_judge.h, pp_follow.h, pp_lanechange.h, pp_episode.h;
-// the judge summary's is pp_summary.h, the sensor model's pp_sensor.h.
+// the judge summary's is pp_summary.h, the sensor model's pp_sensor.h, the tracker's pp_tracker.h.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -55,6 +55,7 @@
 #include "pp_episode.h"
 #include "pp_summary.h"
 #include "pp_sensor.h"
+#include "pp_tracker.h"
 
 using namespace ppd;
 
@@ -64,7 +65,7 @@ using namespace ppd;
 #include "pp_k_cand.h"       // K2: run_candidate, cand_group, k_cand
 #include "pp_k_out.h"        // K3/K4: k_winner, k_winner_st, k_emit
 #include "pp_k_step.h"       // k_cand_small, k_step_small(512), k_plan_frame
-#include "pp_k_world.h"      // k_sim, k_judge, k_follow, k_lane_change, k_sense, k_summary_*, k_synth*, map kernels, k_libm
+#include "pp_k_world.h"      // k_sim, k_judge, k_follow, k_lane_change, k_sense, k_track, k_summary_*, k_synth*, map kernels, k_libm
 #include "pp_k_math.h"       // k_math: the loop's FP64 primitives over arrays (pp_math_eval)
 
 // ================================================================================================
@@ -73,5 +74,5 @@ using namespace ppd;
 #include "pp_host_map.h"     // pp_map, DevState, StreamWS, build_map, dev_init, WorldDev, launch_scenes
 #include "pp_launch.h"       // workspace, launch-shape choices, eval_impl and its launch sequences
 #include "pp_api.h"          // C ABI: params, maps, reserve, pp_eval, debug, timing, synthesis, diagnostics
-#include "pp_api_rollout.h"  // C ABI: rollouts, judge, follow, lane change, summary, sweep, sensor
+#include "pp_api_rollout.h"  // C ABI: rollouts, judge, follow, lane change, summary, sweep, sensor, tracker
 #include "pp_api_frame.h"    // C ABI: pp_plan_batch_host, pp_plan_reset, pp_plan_frame

@@ -480,6 +480,13 @@ bool sense_frame_ok(const pp_scene_batch* tel) {
     return tel->car_stride == 0 || (tel->car_id && tel->car_x && tel->car_y && tel->car_vx && tel->car_vy);
 }
 
+// the tracker's configuration in range and every array of its state (the slot and row arrays where rows > 0)
+bool tracker_ok(const pp_tracker_cfg* c, const pp_tracker* x, int32_t rows) {
+    if (!c || !x || !pptracker::cfg_ok(*c) || !x->frame || !x->n_tracks || !x->n_cars) return false;
+    return rows == 0 || (x->id && x->misses && x->x && x->y && x->vx && x->vy && x->ppp && x->ppv && x->pvv &&
+                         x->car_id && x->car_x && x->car_y && x->car_vx && x->car_vy && x->src);
+}
+
 ppsensor::Truth truth_view(const pp_scene_batch* b) {
     return {b->n_scenes, b->car_stride, b->ego_x, b->ego_y, b->n_cars, b->car_id, b->car_x, b->car_y, b->car_vx,
             b->car_vy};

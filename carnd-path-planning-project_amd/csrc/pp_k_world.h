@@ -1,5 +1,5 @@
 // pp_k_world.h — device: what surrounds the evaluator. The closed-loop rollout's simulator shim, judge
-// and car-following, lane-changing traffic (k_sim, k_judge, k_follow, k_lane_change), the sensor model (k_sense), the judge summary (k_summary_*), scene synthesis (k_synth*), the map tables'
+// and car-following, lane-changing traffic (k_sim, k_judge, k_follow, k_lane_change), the sensor model (k_sense), the tracker (k_track), the judge summary (k_summary_*), scene synthesis (k_synth*), the map tables'
 // kernels (Map::Init, src/main.cpp:89-131) and k_libm. Part of pp_eval.hip's translation unit.
 #pragma once
 
@@ -136,6 +136,16 @@ __global__ __launch_bounds__(256) void k_sense(ppsensor::Truth T, pp_sensor_cfg 
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= T.S) return;
     ppsensor::sense_scene(T, s, cfg, st);
+}
+
+// The tracker (include/pp.h pp_track_frame; csrc/pp_tracker.h): one lane per scene, every array
+// [. * S + s]; no LDS, no per-lane arrays: the merge walks two cursors, one into the rows and one into
+// the old bank, through global memory. Reads the rows (the sensor state's or the telemetry's) and the
+// old bank, writes the other bank and the tracked rows; in a rollout it runs between k_sense and pp_eval.
+__global__ __launch_bounds__(256) void k_track(ppsensor::Truth Z, pp_tracker_cfg cfg, double dt, pp_tracker st) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= Z.S) return;
+    pptracker::track_scene(Z, s, cfg, dt, st);
 }
 
 // ------------------------------------------------------------------------------------------------

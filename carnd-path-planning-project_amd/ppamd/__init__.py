@@ -176,6 +176,24 @@ class Sensor(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in SENSOR_FIELDS]
 
 
+class TrackerCfg(C.Structure):
+    _fields_ = [("meas_pos_sigma", C.c_double), ("meas_pos_sigma_per_m", C.c_double), ("meas_vel_sigma", C.c_double),
+                ("acc_sigma", C.c_double), ("max_coast", C.c_int32), ("_pad", C.c_int32)]
+
+
+# the tracker's state (include/pp.h pp_tracker); "2n": [2 car_stride, S], the two banks of track slots
+TRACK_NONE, TRACK_NEW, TRACK_UPDATED, TRACK_COASTED = range(4)
+TRACK_SLOT_FIELDS = ["id", "misses", "x", "y", "vx", "vy", "ppp", "ppv", "pvv"]
+TRACKER_FIELDS = ([("frame", "i4", None), ("n_tracks", "i4", 2), ("id", "i4", "2n"), ("misses", "i4", "2n")] +
+                  [(k, "f8", "2n") for k in TRACK_SLOT_FIELDS[2:]] +
+                  [("n_cars", "i4", None), ("car_id", "i4", "n"), ("car_x", "f8", "n"), ("car_y", "f8", "n"),
+                   ("car_vx", "f8", "n"), ("car_vy", "f8", "n"), ("src", "i4", "n")])
+
+
+class Tracker(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _, _ in TRACKER_FIELDS]
+
+
 class EpisodeCfg(C.Structure):
     _fields_ = [("n_cars", C.c_int32), ("_pad", C.c_int32), ("ego_speed_min", C.c_double),
                 ("ego_speed_max", C.c_double), ("car_speed_min", C.c_double), ("car_speed_max", C.c_double),
@@ -258,7 +276,8 @@ EXPORTS = ["pp_params_default", "pp_num_candidates", "pp_version", "pp_map_creat
            "pp_lane_change_cfg_default", "pp_traffic_lane_change", "pp_traffic_lane_change_host",
            "pp_rollout_lane_changing", "pp_judge_summary", "pp_judge_summary_host", "pp_rollout_sweep",
            "pp_sensor_cfg_default", "pp_sense_frame", "pp_sense_frame_host", "pp_sensor_gauss", "pp_rollout_sensed",
-           "pp_rollout_sweep_sensed"]
+           "pp_rollout_sweep_sensed", "pp_tracker_cfg_default", "pp_track_frame", "pp_track_frame_host",
+           "pp_rollout_tracked", "pp_rollout_sweep_tracked"]
 
 
 def _load():
@@ -372,6 +391,18 @@ def _load():
     lib.pp_rollout_sensed.restype = C.c_int32
     lib.pp_rollout_sweep_sensed.argtypes = lib.pp_rollout_sweep.argtypes + [C.POINTER(SensorCfg), C.POINTER(Sensor)]
     lib.pp_rollout_sweep_sensed.restype = C.c_int32
+    lib.pp_tracker_cfg_default.argtypes = [C.POINTER(TrackerCfg)]
+    lib.pp_tracker_cfg_default.restype = None
+    lib.pp_track_frame.argtypes = [C.POINTER(SceneBatch), C.POINTER(TrackerCfg), C.c_int32, C.POINTER(Tracker),
+                                   C.c_int32, C.c_void_p]
+    lib.pp_track_frame.restype = C.c_int32
+    lib.pp_track_frame_host.argtypes = [C.POINTER(SceneBatch), C.POINTER(TrackerCfg), C.c_int32, C.POINTER(Tracker)]
+    lib.pp_track_frame_host.restype = C.c_int32
+    lib.pp_rollout_tracked.argtypes = lib.pp_rollout_sensed.argtypes + [C.POINTER(TrackerCfg), C.POINTER(Tracker)]
+    lib.pp_rollout_tracked.restype = C.c_int32
+    lib.pp_rollout_sweep_tracked.argtypes = lib.pp_rollout_sweep_sensed.argtypes + [C.POINTER(TrackerCfg),
+                                                                                    C.POINTER(Tracker)]
+    lib.pp_rollout_sweep_tracked.restype = C.c_int32
     lib.pp_synth_traffic.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.POINTER(SceneBatch),
                                      C.POINTER(Traffic), C.c_int32, C.c_void_p]
     lib.pp_synth_traffic.restype = C.c_int32
@@ -476,7 +507,8 @@ def _zeros(xp, device):
 def _alloc_state(fields, S, n, xp, device):
     """Zero arrays of a field table (JUDGE_FIELDS, FOLLOW_FIELDS, LANE_CHANGE_FIELDS)."""
     mk = _zeros(xp, device)
-    return {k: mk((S,) if lead is None else (n if lead == "n" else lead, S), dt) for k, dt, lead in fields}
+    rows = lambda lead: n if lead == "n" else (2 * n if lead == "2n" else lead)
+    return {k: mk((S,) if lead is None else (rows(lead), S), dt) for k, dt, lead in fields}
 
 
 def _struct(cls, names, d, optional=False):
@@ -917,6 +949,71 @@ def rollout_sensed(m, scenes, traffic, prm, result, follow, lane_change, sensor,
              scfg if scfg is not None else default_sensor_cfg(), sensor_struct(sensor))
 
 
+def default_tracker_cfg(**over) -> TrackerCfg:
+    """pp_tracker_cfg_default (the identity tracker), with fields overridden by keyword."""
+    return _default_cfg(TrackerCfg, lib.pp_tracker_cfg_default, over)
+
+
+def alloc_tracker(S, car_stride=12, xp="numpy", device=None):
+    """Zero-filled tracker state of S scenes x car_stride rows and 2 x car_stride track slots (every
+    scene a fresh episode)."""
+    return _alloc_state(TRACKER_FIELDS, S, car_stride, xp, device)
+
+
+def tracker_struct(x) -> Tracker:
+    return _struct(Tracker, [k for k, _, _ in TRACKER_FIELDS], x)
+
+
+def tracker_to_numpy(x):
+    return _to_numpy(x)
+
+
+def tracked_scenes(scenes, tracker):
+    """The scene dict pp_eval is handed behind a tracker: `scenes` with the tracker state's rows in place
+    of its own (the other arrays, the car table among them, shared)."""
+    return dict(scenes, **{k: tracker[k] for k in SENSED_ROWS})
+
+
+def track_frame(seen, tracker, cfg=None, consume=3, host=None, device=0, stream=None):
+    """pp_track_frame / pp_track_frame_host: one frame of the tracker from `seen`'s ego position and car
+    rows (sensed_scenes(), or the plain truth; only read); `tracker` is updated in place. host=None picks
+    the host twin when the arrays are numpy."""
+    if host is None:
+        host = isinstance(seen["ego_x"], np.ndarray)
+    cfg = cfg if cfg is not None else default_tracker_cfg()
+    b = scene_struct(seen)
+    assert tracker["src"].shape[0] == b.car_stride and tracker["id"].shape[0] == 2 * b.car_stride, \
+        "the tracker state's banks are laid out for another car_stride"
+    X = tracker_struct(tracker)
+    if host:
+        _check(lib.pp_track_frame_host(_ref(b), _ref(cfg), consume, _ref(X)), "pp_track_frame_host")
+    else:
+        _check(lib.pp_track_frame(_ref(b), _ref(cfg), consume, _ref(X), device, stream), "pp_track_frame")
+
+
+def rollout_tracked(m, scenes, traffic, prm, result, follow, lane_change, sensor, tracker, n_frames, consume=3,
+                    sensor_range=300.0, log=None, judge=None, jcfg=None, fcfg=None, lcfg=None, scfg=None, tcfg=None,
+                    device=0, stream=None):
+    """pp_rollout_tracked: rollout_sensed() whose planner sees the sensed rows through the tracker
+    (tracker state updated in place). sensor=None: the tracker works on the truth rows. tcfg=None: the
+    identity tracker."""
+    n, R = int(traffic["n_cars"]), int(scenes["car_id"].shape[0])
+    assert follow["desired"].shape[0] >= n, "follow state holds fewer cars than the traffic"
+    assert tracker["src"].shape[0] == R and tracker["id"].shape[0] == 2 * R, \
+        "the tracker state's banks are laid out for another car_stride"
+    change, sense = (None, None), (None, None)
+    if lane_change is not None:
+        assert lane_change["home"].shape[0] >= n, "lane-change state holds fewer cars than the traffic"
+        change = (lcfg if lcfg is not None else default_lane_change_cfg(), lane_change_struct(lane_change))
+    if sensor is not None:
+        assert sensor["fate"].shape[0] >= R, "sensor state holds fewer rows than the scenes"
+        sense = (scfg if scfg is not None else default_sensor_cfg(), sensor_struct(sensor))
+    _rollout(lib.pp_rollout_tracked, "pp_rollout_tracked", m, scenes, traffic, prm, result, n_frames, consume,
+             sensor_range, log, device, stream, *_judge_stage(judge, jcfg),
+             fcfg if fcfg is not None else default_follow_cfg(), follow_struct(follow), *change, *sense,
+             tcfg if tcfg is not None else default_tracker_cfg(), tracker_struct(tracker))
+
+
 def alloc_judge_stats(rows, bins=64, xp="numpy", device=None):
     """Zero arrays for `rows` rows of summary figures with a histogram of `bins` bins (pp_judge_stats)."""
     mk = _zeros(xp, device)
@@ -996,7 +1093,8 @@ def stats_quantile(stats, row, q, hist_max=HIST_MAX_DEFAULT):
 
 def rollout_sweep(m, sets, S, n_frames, scenes_per_group=None, seed=0x5EED0001, first=0, consume=3,
                   sensor_range=300.0, hist_bins=64, hist_max=HIST_MAX_DEFAULT, ecfg=None, jcfg=None, fcfg=None,
-                  lcfg=None, lane_changes=True, device=0, stream=None, buffers=None, sensors=None, sensor=None):
+                  lcfg=None, lane_changes=True, device=0, stream=None, buffers=None, sensors=None, sensor=None,
+                  trackers=None, tracker=None):
     """pp_rollout_sweep: drives the same S seeded episodes (synth_episode) once per parameter set of
     `sets` (a list of Params) through rollout_lane_changing and summarises each drive per group of
     `scenes_per_group` scenes (None: S), all on the one stream with no host synchronisation. Returns
@@ -1004,7 +1102,9 @@ def rollout_sweep(m, sets, S, n_frames, scenes_per_group=None, seed=0x5EED0001, 
     g, and the drive's buffers (scenes, traffic, result, judge, follow, lane_change: the last set's end
     state), which a later call of the same sizes may pass back in. `sensors` (a list of SensorCfg, one per
     set): pp_rollout_sweep_sensed, set p driven through rollout_sensed with sensors[p]; `sensor` is its
-    state (None: allocated; buffers["sensor"] either way)."""
+    state (None: allocated; buffers["sensor"] either way). `trackers` (a list of TrackerCfg, one per
+    set; sensors=None: identity sensors): pp_rollout_sweep_tracked, set p driven through rollout_tracked
+    with sensors[p] and trackers[p]; `tracker` is its state (buffers["tracker"])."""
     import torch
     dev = torch.device("cuda", device)
     ecfg = ecfg if ecfg is not None else default_episode_cfg()
@@ -1035,6 +1135,8 @@ def rollout_sweep(m, sets, S, n_frames, scenes_per_group=None, seed=0x5EED0001, 
     J, F, O = judge_struct(buffers["judge"]), follow_struct(buffers["follow"]), stats_struct(stats)
     args = (m.handle, arr, _ref(cfg), _ref(ecfg), _ref(jcfg), _ref(fcfg), _ref(lcfg) if lc is not None else None,
             _ref(b), _ref(T), _ref(R), _ref(J), _ref(F), _ref(L), _ref(O), device, stream)
+    if trackers is not None and sensors is None:
+        sensors = [default_sensor_cfg() for _ in range(P)]
     if sensors is None:
         _check(lib.pp_rollout_sweep(*args), "pp_rollout_sweep")
     else:
@@ -1045,7 +1147,18 @@ def rollout_sweep(m, sets, S, n_frames, scenes_per_group=None, seed=0x5EED0001, 
             sensor = alloc_sensor(S, int(buffers["scenes"]["car_id"].shape[0]), xp="torch", device=dev)
         buffers["sensor"] = sensor
         sarr = (SensorCfg * max(P, 1))(*sensors)
-        _check(lib.pp_rollout_sweep_sensed(*args, sarr, _ref(sensor_struct(sensor))), "pp_rollout_sweep_sensed")
+        if trackers is None:
+            _check(lib.pp_rollout_sweep_sensed(*args, sarr, _ref(sensor_struct(sensor))), "pp_rollout_sweep_sensed")
+        else:
+            assert len(trackers) == P, "one tracker per parameter set"
+            if tracker is None:
+                tracker = buffers.get("tracker")
+            if tracker is None:
+                tracker = alloc_tracker(S, int(buffers["scenes"]["car_id"].shape[0]), xp="torch", device=dev)
+            buffers["tracker"] = tracker
+            tarr = (TrackerCfg * max(P, 1))(*trackers)
+            _check(lib.pp_rollout_sweep_tracked(*args, sarr, _ref(sensor_struct(sensor)), tarr,
+                                                _ref(tracker_struct(tracker))), "pp_rollout_sweep_tracked")
     buffers["traffic"]["n_cars"] = int(ecfg.n_cars)
     return stats, buffers
 

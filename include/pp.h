@@ -746,6 +746,96 @@ int32_t pp_rollout_sweep_sensed(pp_map* m, const pp_params* sets, const pp_sweep
                                 pp_judge_stats* stats, int32_t device, void* hip_stream,
                                 const pp_sensor_cfg* sensor_sets, pp_sensor* sstate);
 
+/* ---- tracker: one Kalman filter per sensed car, between the sensor and the planner ------------- */
+/* Sensor fusion gives stable ids, so there is no assignment: per scene the tracker merges its old
+ * tracks with the frame's rows in id order. A car in both is filtered (constant velocity, position
+ * and velocity measured, one 2x2 covariance shared by both axes), a car only in the rows starts a
+ * track at its report, a car only in the tracks coasts on its predicted straight line for up to
+ * max_coast frames and is then deleted. THIS LIBRARY'S OWN definitions (DESIGN.md "Tracker" and
+ * csrc/pp_tracker.h state every formula and its operation order). No gating, no confirmation, no map.
+ * The rows are `seen`'s ego_x, ego_y, n_cars and car rows (the telemetry with a sensor state's rows in
+ * place, or the plain truth), only read: n = clamp(n_cars[s], 0, K), K = seen->car_stride; rows are
+ * expected in ascending id and a row whose id is <= the last accepted row's is skipped. A coasting
+ * track is also deleted where it would leave no room for the rows still to come (reported rows always
+ * fit); with max_coast and every sigma 0 (the default) the tracked rows are the accepted rows bit for
+ * bit. dt = consume x 0.02 s. */
+#define PP_TRACK_NONE      0   /* src of a row r >= n_cars[s]: no track                            */
+#define PP_TRACK_NEW       1   /* first report of the id: the report itself                         */
+#define PP_TRACK_UPDATED   2   /* prediction corrected by the report                                */
+#define PP_TRACK_COASTED   3   /* not reported: the prediction                                      */
+
+typedef struct pp_tracker_cfg {
+    double  meas_pos_sigma;        /* 0 m: the filter's model of the sensor's pos_sigma             */
+    double  meas_pos_sigma_per_m;  /* 0: ... of its pos_sigma_per_m                                 */
+    double  meas_vel_sigma;        /* 0 m/s: ... of its vel_sigma                                   */
+    double  acc_sigma;             /* 0 m/s^2: process noise (white acceleration)                   */
+    int32_t max_coast;             /* 0: frames a track outlives its last report, >= 0              */
+    int32_t _pad;
+} pp_tracker_cfg;                  /* sigmas finite and >= 0; the default: the identity tracker     */
+
+/* Tracker state of a batch (SoA, caller owned; device resident for pp_track_frame and
+ * pp_rollout_tracked, host memory for pp_track_frame_host), S = seen->n_scenes, K = seen->car_stride.
+ * Two banks of K track slots, field [(b * K + k) * S + s], n_tracks[b * S + s]: with f = frame[s] a
+ * call reads bank f & 1 and writes the other. Where f == 0 the old bank counts as empty whatever it
+ * holds, so a state is reused by zeroing `frame` alone. The tracked rows [r * S + s] (the new bank's
+ * tracks, ascending id) and src are written, never read; every src entry is written by every call,
+ * rows at and beyond n_cars[s] are not. */
+typedef struct pp_tracker {
+    int32_t* frame;                /* [S] carried: frames tracked so far in the episode             */
+    int32_t* n_tracks;             /* [2 S]                                                         */
+    int32_t* id;                   /* [2 K S] the banks                                             */
+    int32_t* misses;               /*         frames since the last report                          */
+    double*  x;
+    double*  y;
+    double*  vx;
+    double*  vy;
+    double*  ppp;                  /*         covariance: position, position-velocity, velocity     */
+    double*  ppv;
+    double*  pvv;
+    int32_t* n_cars;               /* [S] tracked rows                                              */
+    int32_t* car_id;               /* [K S] the tracked rows: what pp_eval is handed                */
+    double*  car_x;
+    double*  car_y;
+    double*  car_vx;
+    double*  car_vy;
+    int32_t* src;                  /* [K S] per tracked row: PP_TRACK_*                             */
+} pp_tracker;
+
+void    pp_tracker_cfg_default(pp_tracker_cfg* c);
+/* Tracks ONE frame (no map), for callers with their own loop: hand pp_eval a copy of the telemetry
+ * struct whose n_cars and car_* are the state's. Writes `state` only. PP_ERR_ARG (before any HIP call)
+ * for a NULL argument or array, n_scenes < 0, a car_stride outside 0..PP_MAX_CARS, consume < 1, a
+ * sigma that is negative or not finite, max_coast < 0. Device pointers; asynchronous on hip_stream. */
+int32_t pp_track_frame(const pp_scene_batch* seen, const pp_tracker_cfg* cfg, int32_t consume,
+                       pp_tracker* state, int32_t device, void* hip_stream);
+/* The same on the host (host pointers; the same arithmetic, bit for bit). */
+int32_t pp_track_frame_host(const pp_scene_batch* seen, const pp_tracker_cfg* cfg, int32_t consume,
+                            pp_tracker* state);
+/* pp_rollout_sensed with the tracker: a frame is the sensor on the telemetry (where asked for), the
+ * tracker on the sensed rows (on the truth rows without a sensor), then pp_eval on the tracked rows
+ * (it updates the telemetry's car table from them); every other stage reads and writes the truth and
+ * the log's n_cars is the truth's. tcfg and tstate both NULL: exactly pp_rollout_sensed; one alone is
+ * refused. */
+int32_t pp_rollout_tracked(pp_map* m, pp_scene_batch* telemetry, pp_traffic* traffic,
+                           const pp_params* prm, const pp_rollout_cfg* cfg, pp_result* result,
+                           pp_rollout_log* log, int32_t device, void* hip_stream,
+                           const pp_judge_cfg* jcfg, pp_judge* jstate,
+                           const pp_follow_cfg* fcfg, pp_follow* fstate,
+                           const pp_lane_change_cfg* lcfg, pp_lane_change* lstate,
+                           const pp_sensor_cfg* scfg, pp_sensor* sstate,
+                           const pp_tracker_cfg* tcfg, pp_tracker* tstate);
+/* pp_rollout_sweep_sensed with a tracker per set: set p is driven with sets[p], sensor_sets[p] and
+ * tracker_sets[p] (host memory, n_sets entries each). Per set sstate->frame and tstate->frame are
+ * zeroed on the stream before the drive, and the drive is pp_rollout_tracked. Every set is checked
+ * before the first launch. */
+int32_t pp_rollout_sweep_tracked(pp_map* m, const pp_params* sets, const pp_sweep_cfg* cfg,
+                                 const pp_episode_cfg* ecfg, const pp_judge_cfg* jcfg, const pp_follow_cfg* fcfg,
+                                 const pp_lane_change_cfg* lcfg, pp_scene_batch* telemetry, pp_traffic* traffic,
+                                 pp_result* result, pp_judge* jstate, pp_follow* fstate, pp_lane_change* lstate,
+                                 pp_judge_stats* stats, int32_t device, void* hip_stream,
+                                 const pp_sensor_cfg* sensor_sets, pp_sensor* sstate,
+                                 const pp_tracker_cfg* tracker_sets, pp_tracker* tstate);
+
 /* A batch in HOST memory (the batched onMessage; what a server calls per tick): stages the
  * scenes — and their car table when tab_valid is set, updated in place — through device memory,
  * runs pp_eval on hip_stream and copies winner, n_out, next_x/next_y, cost and status back into
